@@ -3,7 +3,10 @@
 bench.py — throughput of the NeRF train step (learn_nerf/train.py:78-112 restated as HIP kernels)
 on N GPUs of one node.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+  A plain run sets up, warms up, times the K steps and prints the headline line; --full adds everything below that
+  the headline figure does not need (kernel-family timers and rooflines, render-path legs, other workloads, CPU baseline).
+  --dump-outputs DIR writes what the last timed step left to a caller (losses, parameters, Adam moments) as .npy files.
   N > 1: either the driver's launch (python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py
   --gpus N ...), or plain `python bench.py --gpus N`, which starts that launcher itself as a child process before
   anything touches the GPU.  The run fails if the RCCL process group does not have exactly N ranks.
@@ -15,7 +18,7 @@ targets, Flax-default initial weights.  One step = forward + backward + [RCCL al
 Rays shard data-parallel: every rank draws its own 4096 rays (weak scaling), gradients are
 all-reduced (sum) over RCCL and averaged inside the fused Adam kernel.
 
-Rank 0 prints ONE JSON line (see the task contract) with these extra objects:
+Rank 0 prints ONE JSON line (metric, value, unit, ms_per_step, ...); with --full it holds these extra objects:
   roofline     — SURVEY.md 8(d): configs[1] is MFMA-bound, so the dominant kernel's algorithmic FLOP per launch / its
                  mean HIP-event time in the timed region vs the dense bf16 MFMA peak of MI355X (2.5 PFLOP/s,
                  /opt/skills/guides/MI355X_MICROARCH.md).  The dominant launch is nerf_bwd_ls_kernel, the persistent
@@ -65,6 +68,27 @@ def synthetic_batch(n, seed, device):
     d = d / d.norm(dim=-1, keepdim=True)
     c = torch.rand(n, 3, generator=gen) * 2 - 1
     return torch.stack([o, d, c], 1).float().contiguous().to(device)
+
+
+DUMP_MAX_ELEMS = 4 << 20  # per array: 16 MiB of float32, so the parameters and both Adam moments stay under 64 MB
+
+
+def dump_outputs(out_dir, log, loop):
+    """What the last timed step left to its caller: the loss terms it returned and the parameters and Adam moments it
+    updated in place.  An array longer than DUMP_MAX_ELEMS is written as the elements at a fixed seeded sample of its
+    indices (ascending), the same sample for every array of that length."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {f"loss_{k}": v for k, v in log.items()}
+    arrays.update(params=loop.flat, adam_m=loop.state.opt_m, adam_v=loop.state.opt_v)
+    for name, t in arrays.items():
+        t = t.detach().reshape(-1)
+        if t.numel() > DUMP_MAX_ELEMS:
+            idx = torch.randperm(t.numel(), generator=torch.Generator().manual_seed(0))[:DUMP_MAX_ELEMS].sort().values
+            t = t[idx.to(t.device)]
+        a = t.cpu().numpy()
+        np.save(os.path.join(out_dir, f"{name}.npy"), a if a.dtype in (np.float32, np.float64) else a.astype(np.float32))
 
 
 def cpu_baseline(n_rays=1024, steps=4):
@@ -344,6 +368,12 @@ def main():
     ap.add_argument("--backward", default="ls", choices=["ls", "split"],
                     help="nerf: NeRFModel backward = layer-stationary pipeline (default) or the older chain + weight-gradient "
                          "launches (A/B)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline figure, also measure: kernel-family HIP-event timers in the timed loop "
+                         "(kernels, roofline, roofline_hbm), the render-path forward legs, the short ngp / refnerf legs and "
+                         "the CPU baseline; the --no-* options below drop single parts of it")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write the last step's losses, parameters and Adam moments to DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-kernel-timers", action="store_true")
     ap.add_argument("--no-other-workloads", action="store_true", help="skip the short ngp / refnerf legs")
@@ -354,6 +384,9 @@ def main():
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
+    kernel_timers = args.full and not args.no_kernel_timers
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(self_launch(args.gpus))  # before any GPU call in this process
 
@@ -402,7 +435,7 @@ def main():
     for i in range(args.warmup):
         step(Key(i, ray_offset=rank * n), batch)
     barrier()
-    _prof.enable(not args.no_kernel_timers)
+    _prof.enable(kernel_timers)
     t0 = time.perf_counter()
     for i in range(args.steps):
         log = step(Key(args.warmup + i, ray_offset=rank * n), batch)
@@ -416,6 +449,8 @@ def main():
     elapsed = float(t.item())
     ms_per_step = 1e3 * elapsed / args.steps
     value = world * n * (COARSE + FINE) * args.steps / elapsed
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, log, loop)
 
     if rank == 0:
         m_c, m_f = n * COARSE, n * (COARSE + FINE)
@@ -510,7 +545,7 @@ def main():
             out["step_mfma"] = ref_step
         elif args.workload != "nerf":
             del out["step_mfma"]  # the FLOP model is the vanilla NeRFModel's; the hash-grid step is gather/scatter bound
-        if args.workload == "nerf" and args.precision == "bf16":
+        if args.full and args.workload == "nerf" and args.precision == "bf16":
             # the render path: the fused forward without activation dumps, plain bf16 and split precision
             from learn_nerf import ops as _ops
 
@@ -534,7 +569,7 @@ def main():
                 tf = m_f * FLOP_FWD_PER_EVAL / (ms * 1e-3) / 1e12
                 out[key] = dict(ms=round(ms, 4), tflops=round(tf, 1), frac_of_mfma_peak=round(tf / 2500.0, 4), note=note)
             loop.fine.render_precision = "bf16x3"
-        if world == 1 and args.workload == "nerf" and not args.no_other_workloads:
+        if args.full and world == 1 and args.workload == "nerf" and not args.no_other_workloads:
             del step
             loop = None
             torch.cuda.empty_cache()
@@ -544,7 +579,7 @@ def main():
                     out["other_workloads"][wl] = short_leg(wl, n, device, args.table_log2)
                 except Exception as exc:  # a broken secondary leg must not hide the headline measurement
                     out["other_workloads"][wl] = dict(error=f"{type(exc).__name__}: {exc}")
-        if world == 1 and not args.no_cpu_baseline and args.workload == "nerf":
+        if args.full and world == 1 and not args.no_cpu_baseline and args.workload == "nerf":
             out["cpu_baseline"] = cpu_baseline()
     clean = True
     if world > 1 and args.comm_abi_check:  # last: nothing measured above can be disturbed by it

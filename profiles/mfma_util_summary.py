@@ -1,7 +1,7 @@
 """
 MFMA-pipe utilisation per kernel from a rocprofv3 counter pass (csv) collected with
     rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_ACTIVE_INST_VALU SQ_WAVE_CYCLES SQ_WAIT_INST_ANY
-        --output-format csv -- python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline
+        --output-format csv -- python3 bench.py --full --steps 3 --warmup 1 --no-cpu-baseline
 utilisation = SQ_VALU_MFMA_BUSY_CYCLES / (elapsed cycles x 1024 SIMDs), elapsed cycles = GRBM_GUI_ACTIVE / 8
 (rocprofv3 sums GRBM_GUI_ACTIVE over the 8 XCDs; SQ_VALU_MFMA_BUSY_CYCLES counts 32 cycles per 32x32x16 bf16
 MFMA summed over all SIMDs; SQ_WAVE_CYCLES / SQ_ACTIVE_INST_* / SQ_WAIT_* count quad-cycles per wave).

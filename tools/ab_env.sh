@@ -4,7 +4,7 @@ set -e
 cd "$GRAFT_REPO_ROOT"
 VAR=$1; WL=$2; STEPS=${3:-100}
 for val in 1 0 1 0; do
-  env $VAR=$val python bench.py --workload $WL --steps $STEPS --warmup 10 --no-cpu-baseline --no-other-workloads \
+  env $VAR=$val python bench.py --full --workload $WL --steps $STEPS --warmup 10 --no-cpu-baseline --no-other-workloads \
     > gpurun_out/ab_${VAR}_${val}.json 2> gpurun_out/ab_${VAR}_${val}.err
   python - <<PY
 import json

@@ -4,7 +4,7 @@ set -e
 cd "$GRAFT_REPO_ROOT"
 for wl in ${1:-ngp nerf refnerf}; do
   for ov in 1 0; do
-    LNRF_OVERLAP_BACKWARD=$ov python bench.py --workload $wl --steps 100 --warmup 10 --no-cpu-baseline --no-other-workloads \
+    LNRF_OVERLAP_BACKWARD=$ov python bench.py --full --workload $wl --steps 100 --warmup 10 --no-cpu-baseline --no-other-workloads \
       > gpurun_out/ov_${wl}_${ov}.json 2> gpurun_out/ov_${wl}_${ov}.err
     python - <<PY
 import json

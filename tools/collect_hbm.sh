@@ -4,7 +4,7 @@
 set -e
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 WL=$1; TAG=$2
-ARGS="bench.py --workload $WL --steps 3 --warmup 1 --no-cpu-baseline --no-other-workloads"
+ARGS="bench.py --full --workload $WL --steps 3 --warmup 1 --no-cpu-baseline --no-other-workloads"
 rm -rf gpurun_out/_pf gpurun_out/_pw
 rocprofv3 --pmc FETCH_SIZE --output-format csv -d gpurun_out/_pf -o f -- python3 $ARGS > /dev/null 2> gpurun_out/${TAG}_fetch.err
 rocprofv3 --pmc WRITE_SIZE --output-format csv -d gpurun_out/_pw -o w -- python3 $ARGS > /dev/null 2> gpurun_out/${TAG}_write.err
