@@ -33,7 +33,7 @@ extern "C" {
 
 typedef void* lnrf_stream_t;
 
-#define LNRF_VERSION 100 /* 0.1.0 */
+#define LNRF_VERSION 200 /* 0.2.0 */
 
 #define LNRF_OK 0
 #define LNRF_ERR_ARG (-1)
@@ -122,20 +122,10 @@ int lnrf_composite_fwd(const float* rays, int64_t ray_stride, const float* ts, c
  * Upstream gradient per ray: g_out[N,3] if non-NULL, else out_scale*(outputs - targets)
  * (i.e. d/d outputs of mean squared error when out_scale = 2/(3*N_global)).
  * g_aux_w: (host) n_aux weights = d total / d aux_sum[n,k] (same for every ray).
- * Writes g_density[N,T], g_rgb[N,T,3], g_aux[N,T,n_aux]; atomically accumulates
- * g_background[3].  No gradient flows to ts (fine sampling uses stop_gradient,
+ * Writes g_density[N,T], g_rgb[N,T,3], g_aux[N,T,n_aux]; accumulates g_background[3] (may be NULL) in a fixed
+ * order: per-workgroup partial sums in `scratch` (lnrf_composite_bwd_scratch_bytes(n_rays) bytes, 16-byte aligned),
+ * folded by a second launch — bit-reproducible.  No gradient flows to ts (fine sampling uses stop_gradient,
  * render.py:76; stratified ts do not depend on parameters). */
-int lnrf_composite_bwd(const float* ts, const float* t_min, const float* t_max,
-                       const uint8_t* mask, const float* density, const float* rgb,
-                       const float* aux, int32_t n_aux, const float* background, int64_t n_rays,
-                       int32_t t, const float* g_out, const float* outputs, const float* targets,
-                       int64_t target_stride, float out_scale, const float* g_aux_w,
-                       float* g_density, float* g_rgb, float* g_aux, float* g_background,
-                       lnrf_stream_t stream);
-
-/* The same, with the background gradient (the one sum over rays this call forms, render.py:170-176) added in a fixed
- * order: per-workgroup partial sums in `scratch` (lnrf_composite_bwd_scratch_bytes(n_rays) bytes, 16-byte aligned), folded
- * by a second launch — bit-reproducible, where lnrf_composite_bwd lets the workgroups meet in fp32 atomics. */
 int64_t lnrf_composite_bwd_scratch_bytes(int64_t n_rays);
 int lnrf_composite_bwd_det(const float* ts, const float* t_min, const float* t_max, const uint8_t* mask,
                            const float* density, const float* rgb, const float* aux, int32_t n_aux,
@@ -190,14 +180,11 @@ int lnrf_dense_fwd_gated(const float* x, int64_t ldx, const float* w, const floa
                          int32_t k, int32_t n, lnrf_stream_t stream);
 
 /* g_w[K,N] += x[M,K]^T @ g_y[M,N];  g_b[N] += sum_m g_y (g_b may be NULL).
- * x == NULL and gw == NULL: bias gradient only. */
-int lnrf_dense_bwd_weight(const float* x, int64_t ldx, const float* gy, int64_t ldgy, float* gw,
-                          float* gb, int64_t m, int32_t k, int32_t n, lnrf_stream_t stream);
-
-/* The same with a FIXED summation order (bit-reproducible): the splits of the reduction over m leave their partial
- * sums in `scratch` (lnrf_dense_bwd_weight_scratch_bytes(m, k, n) bytes; k = 0 when x / gw are null) and a second launch
- * adds them in order, instead of fp32 atomics whose arrival order changes from run to run.  What the package's exact-fp32
- * path uses (reference: jax.grad through nn.Dense, model.py:51-60, is deterministic on one device). */
+ * x == NULL and gw == NULL: bias gradient only.
+ * FIXED summation order (bit-reproducible): the splits of the reduction over m leave their partial sums in `scratch`
+ * (lnrf_dense_bwd_weight_scratch_bytes(m, k, n) bytes; k = 0 when x / gw are null) and a second launch adds them in
+ * order.  What the package's exact-fp32 path uses (reference: jax.grad through nn.Dense, model.py:51-60, is
+ * deterministic on one device). */
 int64_t lnrf_dense_bwd_weight_scratch_bytes(int64_t m, int32_t k, int32_t n);
 int lnrf_dense_bwd_weight_det(const float* x, int64_t ldx, const float* gy, int64_t ldgy, float* gw, float* gb,
                               int64_t m, int32_t k, int32_t n, void* scratch, int64_t scratch_bytes,
@@ -238,11 +225,8 @@ typedef struct {
 int lnrf_hashgrid_fwd(const lnrf_hashgrid_desc* desc, const float* tables, const float* x, int64_t m,
                       float* enc_t, lnrf_stream_t stream);
 
-/* g_tables += scatter of g_enc_t (same layout as enc_t) through the same indices/weights. */
-int lnrf_hashgrid_bwd(const lnrf_hashgrid_desc* desc, const float* x, int64_t m, const float* g_enc_t,
-                      float* g_tables, lnrf_stream_t stream);
-
-/* Same scatter with caller-provided scratch (lnrf_hashgrid_bwd_scratch_bytes): hashed levels are reduced
+/* g_tables += scatter of g_enc_t (same layout as enc_t) through the same indices/weights, with caller-provided
+ * scratch (lnrf_hashgrid_bwd_scratch_bytes): hashed levels are reduced
  * without global float atomics (bin by 8K-entry table slice, then one workgroup per bucket accumulates in
  * LDS).  u == NULL: value weights (first-order gradient); u [M,3]: derivative weights (see bwd_dir).
  * level_absmax (optional, u == NULL only): n_levels floats, level_absmax[l] >= max |g_enc_t rows 2l, 2l+1|;
@@ -346,7 +330,7 @@ int lnrf_nerf_mlp_fwd(const lnrf_nerf_shape* shape, const void* packed, const fl
 /* The same forward for a backward by lnrf_nerf_mlp_bwd_ls / _ls2 (save must not be NULL): that backward takes the ReLU
  * masks of Dense_0..7 from the saved activations, so their mask slots in `save` are left unwritten (8 KiB per 32
  * evaluations less to store, ~1/4 fewer epilogue instructions).  A save written by this entry must NOT be handed to
- * lnrf_nerf_mlp_bwd / _bwd_chain. */
+ * lnrf_nerf_mlp_bwd_chain. */
 int lnrf_nerf_mlp_fwd_ls(const lnrf_nerf_shape* shape, const void* packed, const float* x,
                          const float* d, const float* rays, int64_t ray_stride, const float* ts,
                          int32_t t, int64_t m, float* density, float* rgb, void* save,
@@ -365,15 +349,9 @@ int lnrf_nerf_mlp_fwd_split(const lnrf_nerf_shape* shape, const void* packed_spl
                             const float* d, const float* rays, int64_t ray_stride, const float* ts,
                             int32_t t, int64_t m, float* density, float* rgb, lnrf_stream_t stream);
 
-/* Backward of the above wrt the parameters: grads[param_count] += d L / d params given
- * g_density[M], g_rgb[M,3] (= d L / d outputs), the forward outputs and the save buffer.
- * Equals lnrf_nerf_mlp_bwd_chain followed by lnrf_nerf_mlp_bwd_weights. */
-int lnrf_nerf_mlp_bwd(const lnrf_nerf_shape* shape, const void* packed, const void* save,
-                      const float* density, const float* rgb, const float* g_density,
-                      const float* g_rgb, int64_t m, void* scratch, float* grads,
-                      lnrf_stream_t stream);
-
-/* Part 1: input-gradient chain (what jax.grad does through model.py:49-60 back to front);
+/* Backward of the above wrt the parameters, grads[param_count] += d L / d params given g_density[M], g_rgb[M,3]
+ * (= d L / d outputs), the forward outputs and the save buffer, in two launches.
+ * Part 1: input-gradient chain (what jax.grad does through model.py:49-60 back to front);
  * writes the pre-activation gradients of every Dense layer into scratch (fragment order). */
 int lnrf_nerf_mlp_bwd_chain(const lnrf_nerf_shape* shape, const void* packed, const void* save,
                             const float* density, const float* rgb, const float* g_density,
@@ -384,7 +362,7 @@ int lnrf_nerf_mlp_bwd_chain(const lnrf_nerf_shape* shape, const void* packed, co
 int lnrf_nerf_mlp_bwd_weights(const lnrf_nerf_shape* shape, const void* save, void* scratch,
                               int64_t m, float* grads, lnrf_stream_t stream);
 
-/* The same backward (jax.grad through model.py:43-62, as lnrf_nerf_mlp_bwd) as a LAYER-STATIONARY pipeline
+/* The same backward (jax.grad through model.py:43-62, as lnrf_nerf_mlp_bwd_chain + _bwd_weights) as a LAYER-STATIONARY pipeline
  * (csrc/nerf_bwd_ls.hip): a head launch (Dense_11, Dense_10, Dense_9 -> dz), then ONE persistent launch in which every
  * CU owns one of Dense_8 ... Dense_1 — W_l^T and the dW_l accumulators stay in its registers for the whole launch — and
  * the 32-evaluation tiles pass from CU to CU (dy handed over through write-through stores and flag words), then the

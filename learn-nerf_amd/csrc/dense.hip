@@ -373,49 +373,7 @@ __global__ __launch_bounds__(256) void gemm_big_kernel(const float* __restrict__
   }
 }
 
-__global__ void col_sum_kernel(const float* __restrict__ g, int64_t ldg, int64_t m, int n,
-                               float* __restrict__ out) {
-  // out[j] += sum_i g[i][j]; grid.x tiles rows (1024 per block), threads stride columns
-  const int64_t rows_per_block = 1024;
-  const int64_t i0 = (int64_t)blockIdx.x * rows_per_block;
-  const int64_t i1 = i0 + rows_per_block < m ? i0 + rows_per_block : m;
-  for (int j = threadIdx.x; j < n; j += blockDim.x) {
-    float s = 0.0f;
-    for (int64_t i = i0; i < i1; ++i) s += g[i * ldg + j];
-    atomicAdd(out + j, s);
-  }
-}
-
-// n % 4 == 0, n <= 256, 16-byte aligned rows: 64 float4 column groups x 4 row lanes per workgroup, 8 independent
-// row loads in flight per thread (the scalar kernel above runs one dependent load-add chain per thread)
 constexpr int kColSumRows = 512;
-__global__ __launch_bounds__(256) void col_sum4_kernel(const float* __restrict__ g, int64_t ldg, int64_t m, int n,
-                                                       float* __restrict__ out) {
-  __shared__ float4 part[4][64];
-  const int cg = threadIdx.x & 63, rl = threadIdx.x >> 6;
-  const int64_t i0 = (int64_t)blockIdx.x * kColSumRows;
-  const int64_t i1 = i0 + kColSumRows < m ? i0 + kColSumRows : m;
-  float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
-  if (4 * cg < n) {
-    for (int64_t i = i0 + rl; i < i1; i += 32) {
-#pragma unroll
-      for (int q = 0; q < 8; ++q) {
-        const int64_t r = i + 4 * q;
-        const float4 v = r < i1 ? *reinterpret_cast<const float4*>(g + r * ldg + 4 * cg) : make_float4(0.f, 0.f, 0.f, 0.f);
-        s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
-      }
-    }
-  }
-  part[rl][cg] = s;
-  __syncthreads();
-  if (rl == 0 && 4 * cg < n) {
-    const float4 a = part[0][cg], b = part[1][cg], c = part[2][cg], d = part[3][cg];
-    atomicAdd(out + 4 * cg + 0, a.x + b.x + c.x + d.x);
-    atomicAdd(out + 4 * cg + 1, a.y + b.y + c.y + d.y);
-    atomicAdd(out + 4 * cg + 2, a.z + b.z + c.z + d.z);
-    atomicAdd(out + 4 * cg + 3, a.w + b.w + c.w + d.w);
-  }
-}
 
 // out[e] += parts[0][e] + parts[1][e] + ... in that order (e < count): the deterministic end of a split reduction
 __global__ __launch_bounds__(256) void dense_fold_kernel(const float* __restrict__ parts, int n_parts, int64_t count,
@@ -607,34 +565,6 @@ extern "C" int lnrf_dense_fwd_gated(const float* x, int64_t ldx, const float* w,
   return launch_gemm(x, ldx, 1, w, n, 1, y, ldy, b, act, 0, m, n, k, 1, as_stream(stream), Gate{y_gate, ldg, act_gate, n});
 }
 
-extern "C" int lnrf_dense_bwd_weight(const float* x, int64_t ldx, const float* gy, int64_t ldgy,
-                                     float* gw, float* gb, int64_t m, int32_t k, int32_t n,
-                                     lnrf_stream_t stream) {
-  LNRF_CHECK_ARG(gy && ((x && gw) || (!x && !gw && gb)), "null pointer");
-  LNRF_CHECK_ARG(m >= 0 && n >= 1 && ldgy >= n && (!x || (k >= 1 && ldx >= k)), "bad sizes");
-  if (m == 0) return LNRF_OK;
-  if (x) {
-    // gw[kk][j] += sum_m x[m][kk] * gy[m][j]: A(i=kk, r=m) = x[m*ldx + kk]
-    const int tiles = ((k + TI - 1) / TI) * ((n + TJ - 1) / TJ);
-    int splits = (int)((2048 + tiles - 1) / tiles);
-    if (splits > 512) splits = 512;  // bounds the atomic adders per output element
-    const int64_t max_splits = (m + 255) / 256;
-    if (splits > max_splits) splits = (int)max_splits;
-    int rc = launch_gemm(x, 1, ldx, gy, ldgy, 1, gw, n, nullptr, 0, 2, k, n, m, splits, as_stream(stream));
-    if (rc != LNRF_OK) return rc;
-  }
-  if (gb) {
-    if (n % 4 == 0 && n <= 256 && ldgy % 4 == 0 && aligned16(gy))
-      hipLaunchKernelGGL(col_sum4_kernel, dim3((unsigned)((m + kColSumRows - 1) / kColSumRows)), dim3(256), 0,
-                         as_stream(stream), gy, ldgy, m, n, gb);
-    else
-      hipLaunchKernelGGL(col_sum_kernel, dim3((unsigned)((m + 1023) / 1024)), dim3(256), 0,
-                         as_stream(stream), gy, ldgy, m, n, gb);
-    LNRF_LAUNCH_CHECK();
-  }
-  return LNRF_OK;
-}
-
 static int wgrad_splits(int64_t m, int k, int n) {
   const int tiles = ((k + TI - 1) / TI) * ((n + TJ - 1) / TJ);
   int splits = (int)((2048 + tiles - 1) / tiles);
@@ -650,8 +580,9 @@ extern "C" int64_t lnrf_dense_bwd_weight_scratch_bytes(int64_t m, int32_t k, int
   return (kernel_parts + bias_parts) * (int64_t)sizeof(float) + 256;
 }
 
-// lnrf_dense_bwd_weight with a fixed summation order: every split of the reduction over m stores its partial sums in
-// `scratch` and a second launch adds them split by split, so two calls on the same inputs agree bit for bit.
+// Weight and bias gradients of a Dense layer, gw[k][n] += x^T gy and gb[n] += column sums of gy (x == gw == nullptr: bias
+// only), with a fixed summation order: every split of the reduction over m stores its partial sums in `scratch` and a
+// second launch adds them split by split, so two calls on the same inputs agree bit for bit.
 extern "C" int lnrf_dense_bwd_weight_det(const float* x, int64_t ldx, const float* gy, int64_t ldgy, float* gw, float* gb,
                                          int64_t m, int32_t k, int32_t n, void* scratch, int64_t scratch_bytes,
                                          lnrf_stream_t stream) {

@@ -203,26 +203,16 @@ __device__ __forceinline__ bf16x8 masked_frag(const f32x16& acc, unsigned bits, 
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ void stream_store(char* p, uint4 v) {
   u32x4 t = {v.x, v.y, v.z, v.w};
-#ifdef LNRF_PLAIN_DUMP_STORES  // A/B: ordinary write-back stores
-  *reinterpret_cast<u32x4*>(p) = t;
-#else
   __builtin_nontemporal_store(t, reinterpret_cast<u32x4*>(p));
-#endif
 }
 
-// Byte offset of fragment (slot, tile) in a dump buffer.  n_slots == 0: slot-major [slot][tile][1 KiB] (a slot's tiles
-// are contiguous; a wave's dumps of one tile are n_tiles KiB apart).  n_slots > 0: tile-major [tile][slot][1 KiB] (a
+// Byte offset of fragment (slot, tile) in a dump buffer of n_slots slots per tile: tile-major [tile][slot][1 KiB] (a
 // tile's n_slots fragments are one contiguous block: the dumping wave writes through one block front to back, and a
-// weight-gradient workgroup reads its layer's 16 + 16 KiB out of consecutive blocks).
-// With LNRF_DUMP_GROUP = G > 1 (a power of two dividing the 8 tiles of a workgroup) the blocks hold G tiles each:
-// [tile / G][slot][tile % G][1 KiB], i.e. the 8 waves of a dumping workgroup fill G KiB runs per slot.
-#ifndef LNRF_DUMP_GROUP
-#define LNRF_DUMP_GROUP 1
-#endif
-constexpr int kDumpGroup = LNRF_DUMP_GROUP;
-static_assert(kDumpGroup >= 1 && (kDumpGroup & (kDumpGroup - 1)) == 0 && kDumpGroup <= 8, "dump group");
+// weight-gradient workgroup reads its layer's 16 + 16 KiB out of consecutive blocks).  Every dump is tile-major; the
+// slot-major form [slot][tile][1 KiB] of n_slots == 0 is not used, but without it the compiler schedules and allocates
+// registers differently in the kernels that write dumps.
 __device__ __forceinline__ int64_t dump_off(int slot, int64_t tile, int64_t n_tiles, int n_slots) {
-  if (n_slots > 0) return (((tile / kDumpGroup) * n_slots + slot) * kDumpGroup + tile % kDumpGroup) * kFragBytes;
+  if (n_slots > 0) return (tile * n_slots + slot) * kFragBytes;
   return ((int64_t)slot * n_tiles + tile) * kFragBytes;
 }
 struct DumpAddr {
@@ -230,28 +220,16 @@ struct DumpAddr {
   int64_t n_tiles;  // tiles in the buffer
   int64_t tile;
   int c, hh;
-  int n_slots = 0;  // 0: slot-major, else tile-major with this many slots per tile
+  int n_slots;  // slots per tile of the buffer
   __device__ __forceinline__ char* at(int slot) const {
     return base + dump_off(slot, tile, n_tiles, n_slots) + dump_lane_off(slot, c, hh);
   }
-  // one fragment of this tile, non-temporal.  LNRF_BUFFER_DUMP_STORES (experiment): tile-major buffers take a buffer
-  // store — the tile's block as scalar base, the slot as scalar offset, the lane's 16 bytes as the only vector operand
-  __device__ __forceinline__ void store(int slot, uint4 v) const {
-#ifdef LNRF_BUFFER_DUMP_STORES
-    if (n_slots > 0 && kDumpGroup == 1) {
-      const __amdgpu_buffer_rsrc_t rs =
-          __builtin_amdgcn_make_buffer_rsrc(base + tile * n_slots * kFragBytes, 0, 0x7FFFFFFF, 0x00020000);
-      const u32x4 t = {v.x, v.y, v.z, v.w};
-      __builtin_amdgcn_raw_buffer_store_b128(t, rs, dump_lane_off(slot, c, hh), slot * kFragBytes, 2);  // 2 = nt
-      return;
-    }
-#endif
-    stream_store(at(slot), v);
-  }
+  // one fragment of this tile, non-temporal
+  __device__ __forceinline__ void store(int slot, uint4 v) const { stream_store(at(slot), v); }
 };
-// which layout the operand buffers of a weight-gradient launch have (slots per tile, 0 = slot-major)
+// slots per tile of the operand buffers of a weight-gradient launch
 struct WgLayout {
-  int x_slots = 0, y_slots = 0;
+  int x_slots, y_slots;
   int interleave = 0;  // 1: split s of a problem takes tiles (i * n_blocks + s) * SPI + u instead of a contiguous range
 };
 
@@ -328,7 +306,7 @@ __device__ __forceinline__ void chain_layer_split(RING& ring, Init init, GetHi b
 // row block of it).  blockIdx -> (problem, K-slice of 32-evaluation steps).  Per step the workgroup
 // stages the X and dy fragments into LDS (global -> VGPR -> LDS, two steps of loads in flight) and
 // every wave reads its operand tiles transposed (ds_read_b64_tr_b16: feature on the lane,
-// evaluation in the registers) for the 32x32x16 MFMA.  Partial sums leave by fp32 atomics.
+// evaluation in the registers) for the 32x32x16 MFMA.  Partial sums leave as per-workgroup slabs.
 // ---------------------------------------------------------------------------------------------
 // operand tile = 32 features (fragment pair starting at frag_even) x 16 evaluations (half q of the
 // step).  Lane l receives feature l&31 and evaluations 16q + 8(l>>5) + j, j = 0..7.
@@ -356,75 +334,51 @@ __device__ __forceinline__ bf16x8 tr_frag(const char* frag_even, int lane, int p
 // global -> VGPR -> LDS staging of one iteration = SPI consecutive 32-evaluation steps
 // (NXF + NYF fragments each, 8 waves).  The registers hold the iteration that is written to LDS
 // after the next barrier; its loads were issued one whole iteration earlier.
-// SPI = steps per iteration (per barrier); PLAIN: ordinary loads instead of non-temporal ones; BUF: buffer loads (scalar
-// base re-anchored at every iteration + 32-bit offsets) instead of flat 64-bit addresses — measured -3 % on the fine-pass
-// launch of NeRFModel (1.55 -> 1.50 ms, three interleaved runs each); tile-major operand buffers only (small offsets)
-template <int NXF, int NYF, int SPI, bool PLAIN = false, bool BUF = false>
+// SPI = steps per iteration (per barrier); PLAIN: ordinary loads instead of non-temporal ones.  The loads are buffer loads
+// (scalar base re-anchored at every iteration + 32-bit offsets, which the tile-major layout keeps small) instead of flat
+// 64-bit addresses — measured -3 % on the fine-pass launch of NeRFModel (1.55 -> 1.50 ms, three interleaved runs each).
+template <int NXF, int NYF, int SPI, bool PLAIN = false>
 struct WgStage {
   static constexpr int kWgSpi = SPI;
   static constexpr int NF = NXF + NYF;
   static constexpr int PER_WAVE = (NF + kWaves - 1) / kWaves;
   static constexpr int STEP_BYTES = NF * kFragBytes;
   static constexpr int ITER_BYTES = kWgSpi * STEP_BYTES;
-  const char* x_src;  // buffer base + lane*16
-  const char* y_src;
-  const char* x_base;  // buffer base (BUF)
+  const char* x_base;  // buffer base
   const char* y_base;
-  int x_slot0, y_slot0, x_slots, y_slots;  // first slot of the operand; slots per tile of its buffer (0: slot-major)
+  int x_slot0, y_slot0, x_slots, y_slots;  // first slot of the operand; slots per tile of its buffer
   int64_t t0, n_tiles;                     // first tile of this K-slice; tiles in the buffers
   int64_t iter_stride, t_end;              // tile of (iteration i, step u) = t0 + i * iter_stride + u, valid below t_end
-  int64_t steps;        // steps in this K-slice
   int wave, lane;
   uint4 rr[kWgSpi][PER_WAVE];
 
   // fragment q of this wave is f = wave + 8q; when NF is not a multiple of 8 the surplus waves of
   // the last round re-load fragment NF-1 (harmless duplicate, keeps the loop branch-free).
   // Steps past the end of the K-slice are staged as zeros (they contribute nothing).
+  // Non-temporal loads leave L2 / Infinity Cache to data that is reused — measured better for the coarse pass (1.4 GB of
+  // operands: 0.58-0.60 vs 0.61 ms); ordinary loads are better for the fine pass (8.8 GB: 1.53 vs 1.57-1.58 ms), so the
+  // launch picks by size.
   __device__ __forceinline__ void load(int64_t iter) {
-    if constexpr (BUF) {
-      const int64_t tb = t0 + iter * iter_stride;      // first tile of the iteration
-      const int64_t tbc = tb < t_end ? tb : t0;         // an address that exists, for the steps past the end
-      const int64_t xo = dump_off(x_slot0, tbc, n_tiles, x_slots), yo = dump_off(y_slot0, tbc, n_tiles, y_slots);
-      const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(x_base) + xo, 0, 0x7FFFFFFF, 0x00020000);
-      const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(y_base) + yo, 0, 0x7FFFFFFF, 0x00020000);
-#pragma unroll
-      for (int u = 0; u < kWgSpi; ++u) {
-        const int64_t tl = tb + u;
-        const bool ok = tl < t_end;
-        const int64_t ta = ok ? tl : tbc;
-        const unsigned keep = ok ? 0xFFFFFFFFu : 0u;  // branch-free zeroing of out-of-range steps
-#pragma unroll
-        for (int q = 0; q < PER_WAVE; ++q) {
-          int f = wave + kWaves * q;
-          if constexpr (NF % kWaves != 0) f = f < NF ? f : NF - 1;
-          const bool isx = f < NXF;
-          const int bo = (int)(isx ? dump_off(x_slot0 + f, ta, n_tiles, x_slots) - xo
-                                   : dump_off(y_slot0 + f - NXF, ta, n_tiles, y_slots) - yo);
-          // cache policy (aux): 0 ordinary, 2 non-temporal
-          const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(isx ? rx : ry, bo + lane * 16, 0, PLAIN ? 0 : 2);
-          rr[u][q] = make_uint4(v[0] & keep, v[1] & keep, v[2] & keep, v[3] & keep);
-        }
-      }
-      return;
-    }
+    const int64_t tb = t0 + iter * iter_stride;      // first tile of the iteration
+    const int64_t tbc = tb < t_end ? tb : t0;         // an address that exists, for the steps past the end
+    const int64_t xo = dump_off(x_slot0, tbc, n_tiles, x_slots), yo = dump_off(y_slot0, tbc, n_tiles, y_slots);
+    const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(x_base) + xo, 0, 0x7FFFFFFF, 0x00020000);
+    const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(y_base) + yo, 0, 0x7FFFFFFF, 0x00020000);
 #pragma unroll
     for (int u = 0; u < kWgSpi; ++u) {
-      const int64_t tl = t0 + iter * iter_stride + u;
+      const int64_t tl = tb + u;
       const bool ok = tl < t_end;
-      const int64_t st = ok ? tl - t0 : 0;
+      const int64_t ta = ok ? tl : tbc;
       const unsigned keep = ok ? 0xFFFFFFFFu : 0u;  // branch-free zeroing of out-of-range steps
 #pragma unroll
       for (int q = 0; q < PER_WAVE; ++q) {
         int f = wave + kWaves * q;
         if constexpr (NF % kWaves != 0) f = f < NF ? f : NF - 1;
-        const char* src = f < NXF ? x_src + dump_off(x_slot0 + f, t0 + st, n_tiles, x_slots)
-                                  : y_src + dump_off(y_slot0 + f - NXF, t0 + st, n_tiles, y_slots);
-        // Non-temporal loads leave L2 / Infinity Cache to data that is reused — measured better for the coarse pass
-        // (1.4 GB of operands: 0.58-0.60 vs 0.61 ms); ordinary loads are better for the fine pass (8.8 GB: 1.53 vs
-        // 1.57-1.58 ms), so the launch picks by size.
-        u32x4 v;
-        if constexpr (PLAIN) v = *reinterpret_cast<const u32x4*>(src);
-        else v = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(src));
+        const bool isx = f < NXF;
+        const int bo = (int)(isx ? dump_off(x_slot0 + f, ta, n_tiles, x_slots) - xo
+                                 : dump_off(y_slot0 + f - NXF, ta, n_tiles, y_slots) - yo);
+        // cache policy (aux): 0 ordinary, 2 non-temporal
+        const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(isx ? rx : ry, bo + lane * 16, 0, PLAIN ? 0 : 2);
         rr[u][q] = make_uint4(v[0] & keep, v[1] & keep, v[2] & keep, v[3] & keep);
       }
     }
@@ -449,17 +403,16 @@ constexpr int kSlabTileFloats = 64 * 16;
 constexpr int kSlabWaveFloats = kSlabMaxTiles * kSlabTileFloats + kSlabMaxTO * 64;
 constexpr int64_t kSlabBlockBytes = (int64_t)kWaves * kSlabWaveFloats * (int64_t)sizeof(float);
 
-// PB supplies x_slot0, y_slot0, do_bias, first_block, n_blocks; EPI maps (out tile, column) and
-// (X fragment, row) to gradient-vector offsets.
-template <int NXF, int NYF, int WI, int WO, int SPI, class EPI, bool PLAIN = false, bool BUF = false, class PB>
+// PB supplies x_slot0, y_slot0, first_block, n_blocks.  The partial sums go to `slabs`; wgrad_reduce_tile() maps them
+// to gradient-vector offsets.
+template <int NXF, int NYF, int WI, int WO, int SPI, bool PLAIN, class PB>
 __device__ __forceinline__ void wgrad_body(const PB& pb, const char* __restrict__ save,
                                            const char* __restrict__ gdump, int64_t n_tiles,
-                                           float* __restrict__ grads, WgLayout lay = WgLayout{},
-                                           float* __restrict__ slabs = nullptr) {
+                                           WgLayout lay, float* __restrict__ slabs) {
   constexpr int NI = NXF / 2, NO = NYF / 2;
   constexpr int TI = (NI + WI - 1) / WI, TO = (NO + WO - 1) / WO;  // tiles per wave
   constexpr bool FULL_I = TI * WI == NI, FULL_O = TO * WO == NO;   // every wave owns TI x TO real tiles
-  using Stage = WgStage<NXF, NYF, SPI, PLAIN, BUF>;
+  using Stage = WgStage<NXF, NYF, SPI, PLAIN>;
   constexpr int kWgSpi = SPI;
   static_assert(WI * WO == kWaves, "wave grid");
   static_assert(NXF % 2 == 0 && NYF % 2 == 0, "fragment pairs");
@@ -471,11 +424,10 @@ __device__ __forceinline__ void wgrad_body(const PB& pb, const char* __restrict_
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wi = wave / WO, wo = wave % WO;
 
-  int64_t per = (n_tiles + pb.n_blocks - 1) / pb.n_blocks;
-  per = (per + kDumpGroup - 1) / kDumpGroup * kDumpGroup;  // K-slices start on a tile group of the dump layout
+  const int64_t per = (n_tiles + pb.n_blocks - 1) / pb.n_blocks;
   int64_t t0 = (int64_t)split * per;
   const int64_t t1 = t0 + per < n_tiles ? t0 + per : n_tiles;
-  int64_t steps = t1 > t0 ? t1 - t0 : 0;
+  const int64_t steps = t1 > t0 ? t1 - t0 : 0;
   int64_t iters = (steps + kWgSpi - 1) / kWgSpi;
   int64_t iter_stride = kWgSpi, t_end = t1;
   if (lay.interleave) {  // the splits of a problem walk the tiles side by side
@@ -483,12 +435,9 @@ __device__ __forceinline__ void wgrad_body(const PB& pb, const char* __restrict_
     iter_stride = (int64_t)pb.n_blocks * kWgSpi;
     t_end = n_tiles;
     iters = t0 < n_tiles ? (n_tiles - t0 + iter_stride - 1) / iter_stride : 0;
-    steps = iters * kWgSpi;
   }
 
   Stage stg;
-  stg.x_src = save + lane * 16;
-  stg.y_src = gdump + lane * 16;
   stg.x_base = save;
   stg.y_base = gdump;
   stg.x_slot0 = pb.x_slot0;
@@ -499,7 +448,6 @@ __device__ __forceinline__ void wgrad_body(const PB& pb, const char* __restrict_
   stg.n_tiles = n_tiles;
   stg.iter_stride = iter_stride;
   stg.t_end = t_end;
-  stg.steps = steps;
   stg.wave = wave;
   stg.lane = lane;
 
@@ -568,66 +516,31 @@ __device__ __forceinline__ void wgrad_body(const PB& pb, const char* __restrict_
     if (i + 1 < iters) compute(c1);
   }
 
-#ifdef LNRF_NO_FLUSH
-  if (n_tiles >= 0) return;  // timing experiment only (results are wrong): what the epilogue below costs
-#endif
-  if (slabs != nullptr) {
-    // Slab epilogue: the workgroup's accumulators leave as they stand — [workgroup][wave][tile a * TO + b][4][lane][4 f32],
-    // 4 KiB per tile written as four 1 KiB store instructions — plus the per-lane bias partial sums of the wi == 0 waves;
-    // wgrad_reduce_tile() folds the slabs of a problem in a fixed order and runs the index mapping below once.  Against
-    // fp32 atomics (memory-side, ~1.3 TB/s of added bytes chip-wide: 62-67 us for the ~100 MB of one NeRFModel launch)
-    // the partial sums move at store / load rates, and the gradient no longer depends on arrival order.
-    float* __restrict__ mine = slabs + ((int64_t)blockIdx.x * kWaves + wave) * kSlabWaveFloats;
+  // Slab epilogue: the workgroup's accumulators leave as they stand — [workgroup][wave][tile a * TO + b][4][lane][4 f32],
+  // 4 KiB per tile written as four 1 KiB store instructions — plus the per-lane bias partial sums of the wi == 0 waves;
+  // wgrad_reduce_tile() folds the slabs of a problem in a fixed order and maps them to the gradient vector.  Against
+  // fp32 atomics (memory-side, ~1.3 TB/s of added bytes chip-wide: 62-67 us for the ~100 MB of one NeRFModel launch)
+  // the partial sums move at store / load rates, and the gradient no longer depends on arrival order.
+  float* __restrict__ mine = slabs + ((int64_t)blockIdx.x * kWaves + wave) * kSlabWaveFloats;
 #pragma unroll
-    for (int a = 0; a < TI; ++a)
+  for (int a = 0; a < TI; ++a)
 #pragma unroll
-      for (int b = 0; b < TO; ++b) {
-        // [tile][v][lane][4 f32]: every store instruction writes 1 KiB contiguous
-        float4* dst = reinterpret_cast<float4*>(mine + (a * TO + b) * kSlabTileFloats) + lane;
+    for (int b = 0; b < TO; ++b) {
+      // [tile][v][lane][4 f32]: every store instruction writes 1 KiB contiguous
+      float4* dst = reinterpret_cast<float4*>(mine + (a * TO + b) * kSlabTileFloats) + lane;
 #pragma unroll
-        for (int v = 0; v < 4; ++v)
-          dst[64 * v] = make_float4(acc[a][b][4 * v], acc[a][b][4 * v + 1], acc[a][b][4 * v + 2], acc[a][b][4 * v + 3]);
-      }
-    if (wi == 0) {
-#pragma unroll
-      for (int b = 0; b < TO; ++b) mine[kSlabTileFloats * kSlabMaxTiles + b * 64 + lane] = bsum[b];
+      for (int v = 0; v < 4; ++v)
+        dst[64 * v] = make_float4(acc[a][b][4 * v], acc[a][b][4 * v + 1], acc[a][b][4 * v + 2], acc[a][b][4 * v + 3]);
     }
-    return;
+  if (wi == 0) {
+#pragma unroll
+    for (int b = 0; b < TO; ++b) mine[kSlabTileFloats * kSlabMaxTiles + b * 64 + lane] = bsum[b];
   }
-  // epilogue: atomically add the partial dW tiles / bias sums
-  const int colr = lane & 31, hh = lane >> 5;
-  static_for<TO>([&](auto b_) {
-    constexpr int b = decltype(b_)::value;
-    const int ot = wo + WO * b;
-    int out_idx = -1, out_dim = 1;
-    int64_t w_off = 0, b_off = 0;
-    if (ot < NO) EPI::cols(pb, ot, colr, out_idx, out_dim, w_off, b_off);
-    if (wi == 0 && pb.do_bias) {
-      float sacc = bsum[b];
-      sacc += __shfl_xor(sacc, 32, 64);
-      if (hh == 0 && out_idx >= 0 && b_off >= 0) atomicAdd(grads + b_off + out_idx, sacc);
-    }
-    const int row_lim = EPI::row_limit(pb, ot);
-    static_for<TI>([&](auto a_) {
-      constexpr int a = decltype(a_)::value;
-      const int it = wi + WI * a;
-      static_for<16>([&](auto q_) {
-        constexpr int qq = decltype(q_)::value;
-        const int r = (qq & 3) + 8 * (qq >> 2) + 4 * hh;  // row in the 32-feature tile
-        const int f = 2 * it + (r >> 4);                   // k-step slot within X
-        const int r16 = r & 15;
-        const int in_idx = EPI::row(pb, f, r16);  // kernel row of that X feature, -1 = padding
-        if (it < NI && out_idx >= 0 && in_idx >= 0 && in_idx < row_lim)
-          atomicAdd(grads + w_off + (int64_t)in_idx * out_dim + out_idx,
-                    acc[a][b][qq]);
-      });
-    });
-  });
 }
 
 // A 4-wave workgroup folds ONE accumulator tile (wave w of the producing workgroups, tile j = a * TO + b) of a problem
 // over the problem's n_blocks slabs: wave q sums the slabs q, q + 4, ... in order, the four partial sums meet in LDS and
-// wave 0 adds them (q = 0..3) and applies the same index mapping as the atomic epilogue of wgrad_body.  The order of
+// wave 0 adds them (q = 0..3) and maps the sums to gradient-vector offsets (EPI).  The order of
 // every addition is fixed and every parameter has exactly one owner tile (plain read-modify-write): bit-reproducible.
 constexpr int kSlabReduceWaves = 4;  // 8 measured no faster (finish phase 0.67 vs 0.65 ms, Ref-NeRF step unchanged)
 template <int NXF, int NYF, int WI, int WO, class EPI, class PB>

@@ -598,17 +598,6 @@ static int check_desc(const lnrf_hashgrid_desc* d) {
 
 static_assert(sizeof(HashGridDesc) == sizeof(lnrf_hashgrid_desc), "descriptor layout");
 
-// experiment builds only (common.h): LNRF_HASHGRID_LDS=0 turns the LDS-staged gather off, LNRF_HASHGRID_XCD=0 selects the
-// plain (chunk, level) grid of the gather
-static bool lds_staging_enabled() {
-  static const bool on = !exp_env_is("LNRF_HASHGRID_LDS", '0');
-  return on;
-}
-static bool xcd_mapping_enabled() {
-  static const bool on = !exp_env_is("LNRF_HASHGRID_XCD", '0');
-  return on;
-}
-
 // Relative cost of one sample of a level in the gather, measured alone at 786,432 samples (tools/
 // hashgrid_level_probe.py): dense levels 12 us, hashed levels 17 us at 4 cells per entry, 27 us at 32, 31 us beyond
 // (more and more of the 8 corners fall into different cache lines).
@@ -690,11 +679,11 @@ extern "C" int lnrf_hashgrid_jvp(const lnrf_hashgrid_desc* desc, const float* ta
   LevelList staged, direct;
   staged.n = direct.n = 0;
   for (int l = 0; l < d.n_levels; ++l) {
-    if (lds_staging_enabled() && !d.hashed[l] && d.table_size[l] <= kStageEntries && m >= 16384)
+    if (!d.hashed[l] && d.table_size[l] <= kStageEntries && m >= 16384)
       staged.level[staged.n++] = l;
     else direct.level[direct.n++] = l;
   }
-  if (direct.n > 0 && xcd_mapping_enabled() && (m + 255) / 256 * direct.n <= (int64_t)1 << 28) {
+  if (direct.n > 0 && (m + 255) / 256 * direct.n <= (int64_t)1 << 28) {
     unsigned grid = 0;
     const XcdPlan plan = make_xcd_plan(d, direct, m, &grid);
     if (grid == 0) {
@@ -727,11 +716,6 @@ extern "C" int lnrf_hashgrid_jvp(const lnrf_hashgrid_desc* desc, const float* ta
     LNRF_LAUNCH_CHECK();
   }
   return LNRF_OK;
-}
-
-extern "C" int lnrf_hashgrid_bwd(const lnrf_hashgrid_desc* desc, const float* x, int64_t m, const float* g_enc_t,
-                                 float* g_tables, lnrf_stream_t stream) {
-  return lnrf_hashgrid_bwd_dir(desc, x, nullptr, m, g_enc_t, g_tables, stream);
 }
 
 extern "C" int lnrf_hashgrid_input_grad(const lnrf_hashgrid_desc* desc, const float* tables, const float* x,

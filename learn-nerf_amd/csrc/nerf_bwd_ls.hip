@@ -97,12 +97,11 @@ __device__ __forceinline__ void ls_poll(const unsigned* word, unsigned lds_dst) 
   asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dword %1, %2 sc1\n\ts_mov_b32 m0, %0"
                : "=&s"(keep) : "v"(zero), "s"(word), "s"(lds_dst) : "memory");
 }
-template <int IMM, bool SC1>
+template <int IMM>
 __device__ __forceinline__ void ls_store16(char* base, unsigned voff, u32x4 v) {
   // The s_nop covers the hazard the compiler handles for its own stores and cannot see here: a store of more than 64 bits
   // reads its data registers for a few cycles after issue, and the next instruction may be a VALU write of one of them.
-  if constexpr (SC1) asm volatile("global_store_dwordx4 %0, %1, %2 offset:%c3 sc1\n\ts_nop 1" : : "v"(voff), "v"(v), "s"(base), "i"(IMM) : "memory");
-  else asm volatile("global_store_dwordx4 %0, %1, %2 offset:%c3\n\ts_nop 1" : : "v"(voff), "v"(v), "s"(base), "i"(IMM) : "memory");
+  asm volatile("global_store_dwordx4 %0, %1, %2 offset:%c3 sc1\n\ts_nop 1" : : "v"(voff), "v"(v), "s"(base), "i"(IMM) : "memory");
 }
 __device__ __forceinline__ void ls_flag_store(unsigned* word, unsigned value) {
   unsigned zero = 0u;
@@ -374,21 +373,11 @@ __global__ __launch_bounds__(kLsThreads) void nerf_bwd_ls_kernel(LsArgs args) {
         const unsigned xw = w == 0 ? xm.x : (w == 1 ? xm.y : (w == 2 ? xm.z : xm.w));
         ov[w] = relu_gate_pair(__builtin_bit_cast(unsigned, pk), xw);
         if constexpr (w == 3) {
-#ifdef LS_PLAIN_DY_STORES
-          ls_store16<f * kFragBytes, false>(ob, sh ? st_voff1 : st_voff0, ov);
-#else
-          ls_store16<f * kFragBytes, true>(ob, sh ? st_voff1 : st_voff0, ov);
-#endif
+          ls_store16<f * kFragBytes>(ob, sh ? st_voff1 : st_voff0, ov);
           if constexpr (f < 3) xm = x_mask(std::integral_constant<int, (f < 3 ? f + 1 : 3)>{});
         }
       }
-#ifdef LS_DMA_IN_B
-      if constexpr ((e & 1) == 0 && e < 8) ls_dma16<(e / 2) * kFragBytes, false>(nxb, dma_voff, ndst);
-      if constexpr ((e & 1) == 0 && e >= 8) ls_dma16<((e - 8) / 2) * kFragBytes, true>(nyb, dma_voff, ndst + 16 * kFragBytes);
-#endif
-#ifndef LS_NO_SB_B
       __builtin_amdgcn_sched_barrier(0);
-#endif
     });
 
     LS_STAMP(4);
@@ -556,9 +545,8 @@ static int64_t ls_dump_bytes(int64_t m) { return (int64_t)kGradSlots * nerf_tile
 // workgroups of the three small problems (x_emb x [dy0 | dy5], [z | d_emb] x dy10m, h10 x dy11), in proportion to the bytes
 // they stream per tile (36, 28, 10 KiB)
 static int ls_small_blocks(int i) {
-  static const int total = exp_env_int("LNRF_LS_SMALL_BLOCKS", 256);  // experiment builds only (common.h)
   const int share[3] = {36, 28, 10};
-  return total * share[i] / 74;
+  return 256 * share[i] / 74;
 }
 static int64_t ls_small_slab_bytes() { return 512 * kSlabBlockBytes; }
 static int64_t ls_counter_bytes() { return ((int64_t)kLsMaxPipelines * kLsStages * kLsCounterStride + 64) * (int64_t)sizeof(unsigned); }

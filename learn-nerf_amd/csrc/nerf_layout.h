@@ -313,8 +313,8 @@ constexpr int64_t kRefPackDirBiasOff = kRefPackDirBwdOff + (int64_t)kDirBwdFrags
 constexpr int64_t kRefPackBytes = kRefPackDirBiasOff + 1024;
 
 // ---- saved activations / gradient dumps -------------------------------------------------------
-// Both buffers hold 1 KiB fragments addressed by (slot, tile) through dump_off() (tile-major [tile][slot] unless built with
-// -DLNRF_DUMP_SLOT_MAJOR); a slot is one k-step (16 features) of one tensor.
+// Both buffers hold 1 KiB fragments addressed by (slot, tile) through dump_off() (tile-major [tile][slot]); a slot is one
+// k-step (16 features) of one tensor.
 // Inside the 1 KiB block lane (c, hh) of frag slot F stores its 16 bytes at dump_lane_off():
 // the permutation makes the transposed LDS reads of the weight-gradient kernel conflict-free.
 NL_HD constexpr int dump_lane_off(int slot, int c, int hh) {
@@ -336,13 +336,9 @@ constexpr int kGradDy11 = 0;            // 2 slots (second is zero padding)
 constexpr int kGradDy10m = 2;           // 10 slots: 8 for Dense_10 outputs, slot 8 = logit, slot 9 zero
 constexpr int kGradDy = 12;             // dy8, dy7, dy6, dy4, dy3, dy2, dy1, dy0, dy5: 16 slots each (grad_dy_slot)
 constexpr int kGradSlots = kGradDy + 9 * 16;  // 156
-// NeRFModel dump layout: tile-major unless built with -DLNRF_DUMP_SLOT_MAJOR (A/B; see fused_chain.h dump_off)
-#ifdef LNRF_DUMP_SLOT_MAJOR
-constexpr int kSaveTileSlots = 0, kGradTileSlots = 0, kDirSaveTileSlots = 0, kDirGradTileSlots = 0;
-#else
+// slots per tile of the tile-major dumps (fused_chain.h dump_off)
 constexpr int kSaveTileSlots = kSaveSlots, kGradTileSlots = kGradSlots;
 constexpr int kDirSaveTileSlots = kDirSaveSlots, kDirGradTileSlots = kDirGradSlots;  // Ref-NeRF directional block
-#endif
 // dy5 sits behind dy0: x_emb^T [dy0 | dy5] (Dense_0 and rows 256.. of Dense_5) is ONE weight-gradient problem
 NL_HD constexpr int grad_dy_pos(int l) { return l == 5 ? 8 : (l > 5 ? 8 - l : 7 - l); }
 NL_HD constexpr int grad_dy_slot(int l) { return kGradDy + grad_dy_pos(l) * 16; }

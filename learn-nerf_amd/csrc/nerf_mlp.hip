@@ -408,14 +408,14 @@ __global__ __launch_bounds__(kThreads) void nerf_bwd_chain_kernel(
 // row block of it).  blockIdx -> (problem, K-slice of 32-evaluation steps).  Per step the workgroup
 // stages the X and dy fragments into LDS (global -> VGPR -> LDS, two steps of loads in flight) and
 // every wave reads its operand tiles transposed (ds_read_b64_tr_b16: feature on the lane,
-// evaluation in the registers) for the 32x32x16 MFMA.  Partial sums leave by fp32 atomics.
+// evaluation in the registers) for the 32x32x16 MFMA.  Partial sums leave as per-workgroup slabs that
+// nerf_wgrad_reduce_kernel folds in a fixed order.
 // ---------------------------------------------------------------------------------------------
 // One launch for every Dense layer of the model: blockIdx -> problem -> operand-shape body.
 // Problems are listed heaviest first so that the small ones fill the tail of the launch.
 template <bool PLAIN>
 __global__ __launch_bounds__(kThreads) void nerf_wgrad_kernel(WgradArgs args, const char* __restrict__ save,
-                                                              const char* __restrict__ gdump,
-                                                              int64_t n_tiles, float* __restrict__ grads,
+                                                              const char* __restrict__ gdump, int64_t n_tiles,
                                                               WgLayout lay, float* __restrict__ slabs) {
   WgradProblem pb = args.p[0];
 #pragma unroll
@@ -423,14 +423,14 @@ __global__ __launch_bounds__(kThreads) void nerf_wgrad_kernel(WgradArgs args, co
     if (i < args.n_problems && (int)blockIdx.x >= args.p[i].first_block) pb = args.p[i];
   switch (pb.shape) {
     // steps per barrier chosen so that every body keeps ~60 KB of loads in flight per workgroup
-    case 0: wgrad_body<16, 16, 4, 2, 2, NerfWgradEpi, PLAIN, (kSaveTileSlots > 0)>(pb, save, gdump, n_tiles, grads, lay, slabs); break;
-    case 1: wgrad_body<16, 10, 4, 2, 2, NerfWgradEpi, PLAIN, (kSaveTileSlots > 0)>(pb, save, gdump, n_tiles, grads, lay, slabs); break;
-    case 2: wgrad_body<4, 16, 2, 4, 3, NerfWgradEpi, PLAIN, (kSaveTileSlots > 0)>(pb, save, gdump, n_tiles, grads, lay, slabs); break;
-    case 3: wgrad_body<2, 10, 1, 8, 5, NerfWgradEpi, PLAIN, (kSaveTileSlots > 0)>(pb, save, gdump, n_tiles, grads, lay, slabs); break;
-    case 5: wgrad_body<18, 8, 4, 2, 2, NerfWgradEpi, PLAIN, (kSaveTileSlots > 0)>(pb, save, gdump, n_tiles, grads, lay, slabs); break;  // Ref-NeRF Dense_9
-    case 6: wgrad_body<18, 10, 4, 2, 2, NerfWgradEpi, PLAIN, (kSaveTileSlots > 0)>(pb, save, gdump, n_tiles, grads, lay, slabs); break;  // [z | d_emb] x dy10m
-    case 7: wgrad_body<4, 32, 2, 4, 2, NerfWgradEpi, PLAIN, (kSaveTileSlots > 0)>(pb, save, gdump, n_tiles, grads, lay, slabs); break;   // x_emb x [dy0 | dy5]
-    default: wgrad_body<8, 2, 4, 2, 6, NerfWgradEpi, PLAIN, (kSaveTileSlots > 0)>(pb, save, gdump, n_tiles, grads, lay, slabs); break;
+    case 0: wgrad_body<16, 16, 4, 2, 2, PLAIN>(pb, save, gdump, n_tiles, lay, slabs); break;
+    case 1: wgrad_body<16, 10, 4, 2, 2, PLAIN>(pb, save, gdump, n_tiles, lay, slabs); break;
+    case 2: wgrad_body<4, 16, 2, 4, 3, PLAIN>(pb, save, gdump, n_tiles, lay, slabs); break;
+    case 3: wgrad_body<2, 10, 1, 8, 5, PLAIN>(pb, save, gdump, n_tiles, lay, slabs); break;
+    case 5: wgrad_body<18, 8, 4, 2, 2, PLAIN>(pb, save, gdump, n_tiles, lay, slabs); break;  // Ref-NeRF Dense_9
+    case 6: wgrad_body<18, 10, 4, 2, 2, PLAIN>(pb, save, gdump, n_tiles, lay, slabs); break;  // [z | d_emb] x dy10m
+    case 7: wgrad_body<4, 32, 2, 4, 2, PLAIN>(pb, save, gdump, n_tiles, lay, slabs); break;   // x_emb x [dy0 | dy5]
+    default: wgrad_body<8, 2, 4, 2, 6, PLAIN>(pb, save, gdump, n_tiles, lay, slabs); break;
   }
 }
 
@@ -551,7 +551,8 @@ extern "C" int64_t lnrf_nerf_packed_bytes(const lnrf_nerf_shape* s) {
 extern "C" int64_t lnrf_nerf_save_bytes(const lnrf_nerf_shape* s, int64_t m) {
   return shape_supported(s) ? (int64_t)kSaveSlots * tiles_for(m) * kFragBytes : -1;
 }
-// weight-gradient workgroups of one NeRFModel launch (sum of the per-problem counts in lnrf_nerf_mlp_bwd_weights)
+// workgroups of one NeRFModel weight-gradient launch (sum of the per-problem counts in lnrf_nerf_mlp_bwd_weights), and
+// the most any launch_nerf_wgrad call may use: every caller's slab region holds this many slabs
 constexpr int kNerfWgradBlocks = 512;
 static int64_t grad_dump_bytes(int64_t m) { return (int64_t)kGradSlots * tiles_for(m) * kFragBytes; }
 extern "C" int64_t lnrf_nerf_bwd_scratch_bytes(const lnrf_nerf_shape* s, int64_t m) {
@@ -698,34 +699,22 @@ extern "C" int lnrf_nerf_mlp_bwd_chain(const lnrf_nerf_shape* shape, const void*
   return LNRF_OK;
 }
 
-extern "C" int lnrf_nerf_mlp_bwd(const lnrf_nerf_shape* shape, const void* packed, const void* save,
-                                 const float* density, const float* rgb, const float* g_density,
-                                 const float* g_rgb, int64_t m, void* scratch, float* grads,
-                                 lnrf_stream_t stream) {
-  int rc = lnrf_nerf_mlp_bwd_chain(shape, packed, save, density, rgb, g_density, g_rgb, m, scratch, stream);
-  if (rc) return rc;
-  return lnrf_nerf_mlp_bwd_weights(shape, save, scratch, m, grads, stream);
-}
-
 int lnrf::launch_nerf_wgrad(const WgradArgs& args, int blocks, const void* xbuf, const void* ybuf, int64_t n_tiles,
                             float* grads, hipStream_t stream, WgLayout lay, float* slabs, bool plain, bool fold) {
+  LNRF_CHECK_ARG(slabs != nullptr && blocks <= kNerfWgradBlocks, "needs slabs for at most 512 workgroups");
   const int lds = 2 * 2 * 36 * kFragBytes;  // largest body: 2 buffers x 2 steps x (4 + 32) fragments
   hipError_t e = hipFuncSetAttribute(plain ? reinterpret_cast<const void*>(nerf_wgrad_kernel<true>)
                                            : reinterpret_cast<const void*>(nerf_wgrad_kernel<false>),
                                      hipFuncAttributeMaxDynamicSharedMemorySize, lds);
   if (e != hipSuccess) return hip_fail(e, "hipFuncSetAttribute(max dynamic LDS)");
-  {
-    static const int il = exp_env_int("LNRF_WGRAD_INTERLEAVE", -1);  // experiment builds only (common.h): overrides the caller
-    if (il >= 0) lay.interleave = il;
-  }
   if (plain)
     hipLaunchKernelGGL(nerf_wgrad_kernel<true>, dim3((unsigned)blocks), dim3(kThreads), lds, stream, args,
-                       (const char*)xbuf, (const char*)ybuf, n_tiles, grads, lay, slabs);
+                       (const char*)xbuf, (const char*)ybuf, n_tiles, lay, slabs);
   else
     hipLaunchKernelGGL(nerf_wgrad_kernel<false>, dim3((unsigned)blocks), dim3(kThreads), lds, stream, args,
-                       (const char*)xbuf, (const char*)ybuf, n_tiles, grads, lay, slabs);
+                       (const char*)xbuf, (const char*)ybuf, n_tiles, lay, slabs);
   LNRF_LAUNCH_CHECK();
-  if (slabs != nullptr && fold) {  // room for `blocks` slabs of kSlabBlockBytes is the caller's business
+  if (fold) {
     hipLaunchKernelGGL(nerf_wgrad_reduce_kernel, dim3((unsigned)(args.n_problems * kWaves * kSlabMaxTiles)), dim3(64 * kSlabReduceWaves), 0, stream, args,
                        (const float*)slabs, grads);
     LNRF_LAUNCH_CHECK();
@@ -744,29 +733,17 @@ extern "C" int lnrf_nerf_mlp_bwd_weights(const lnrf_nerf_shape* shape, const voi
   if (m == 0) return LNRF_OK;
   const int64_t n_tiles = tiles_for(m);
   hipStream_t st = as_stream(stream);
-  int rc;
-  // weight-gradient problems: ONE launch, heaviest problems first, blocks proportional to bytes
+  // weight-gradient problems: ONE launch, heaviest problems first, blocks proportional to bytes (512 in all)
   WgradArgs a;
-  int blocks[13] = {48, 48, 48, 48, 47, 47, 47, 47, 39, 30, 30, 18, 15};
-  {
-    // experiment builds only: LNRF_WGRAD_BLOCK_SCALE=<percent> scales the per-problem workgroup counts (100 = 512 total)
-    static const int pct = exp_env_int("LNRF_WGRAD_BLOCK_SCALE", 100);
-    if (pct > 0 && pct != 100)
-      for (int i = 0; i < 13; ++i) blocks[i] = (blocks[i] * pct + 50) / 100 < 1 ? 1 : (blocks[i] * pct + 50) / 100;
-  }
+  const int blocks[13] = {48, 48, 48, 48, 47, 47, 47, 47, 39, 30, 30, 18, 15};
   const int first = build_wgrad_problems(a, blocks, (n_tiles + 5) / 6);
-  (void)rc;
-  // experiment builds only: LNRF_WGRAD_ATOMICS=1 keeps the older fp32-atomic epilogue (A/B)
-  static const bool atomics = exp_env_is("LNRF_WGRAD_ATOMICS", '1');
-  float* slabs = (atomics || first > kNerfWgradBlocks)
-                     ? nullptr
-                     : reinterpret_cast<float*>(reinterpret_cast<char*>(scratch) + grad_dump_bytes(m));
+  float* slabs = reinterpret_cast<float*>(reinterpret_cast<char*>(scratch) + grad_dump_bytes(m));
   // operand loads (fused_chain.h WgStage::load): ordinary for the big (fine-pass) launch, non-temporal for the small one —
-  // measured on this model only (the Ref-NeRF launches are faster with non-temporal loads at every size);
-  // (experiment builds: LNRF_WGRAD_PLAIN_TILES overrides the threshold, in tiles of 32 evaluations)
-  static const int64_t plain_from = exp_env_int("LNRF_WGRAD_PLAIN_TILES", 16384);
+  // measured on this model only (the Ref-NeRF launches are faster with non-temporal loads at every size); in tiles of
+  // 32 evaluations
+  constexpr int64_t kPlainFrom = 16384;
   return launch_nerf_wgrad(a, first, save, scratch, n_tiles, grads, st, WgLayout{kSaveTileSlots, kGradTileSlots}, slabs,
-                           n_tiles >= plain_from);
+                           n_tiles >= kPlainFrom);
 }
 
 #ifdef LNRF_TIMELINE

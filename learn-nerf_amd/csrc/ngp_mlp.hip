@@ -7,8 +7,8 @@
 // converted in place into the B operand of the next one, the packed A-fragment stream (26 + 20 fragments)
 // goes through the shared LDS ring.  The network is so small that the backward kernel recomputes the
 // forward (26 MFMAs) instead of reading saved activations, then runs the transposed chain, writes
-// d loss / d enc feature-major for the hash-grid scatter, and dumps X / dy fragments (about 1 KiB per
-// evaluation) for the shared split-K weight-gradient body.
+// d loss / d enc feature-major for the hash-grid scatter, and forms the weight gradients in the same
+// launch (see NgpWgradProblem).
 // Precision: bf16 operands, fp32 accumulate, fp32 bias / activations / directional encoding.
 
 #include "fused_chain.h"
@@ -44,11 +44,6 @@ constexpr int ngp_total_count(int ne) { return ngp_bwd_base(kNgpLayers, ne); }
 constexpr int ngp_bias_base(int l) { return l == 0 ? 0 : (l == 1 ? 64 : (l == 2 ? 96 : (l == 3 ? 160 : 224))); }
 __host__ __device__ constexpr int ngp_out_dim(int l) { return l == 1 ? kNgpDensityDim : (l == 4 ? 3 : kNgpHidden); }
 
-// dump slots of the backward scratch ([slot][tile][1 KiB]): X tensors then dy tensors
-constexpr int kNgpXEnc = 0, kNgpXH0 = 2, kNgpXCat = 6, kNgpXC1 = 10, kNgpXC2 = 14;
-constexpr int kNgpDy0 = 18, kNgpDy1 = 22, kNgpDy2 = 24, kNgpDy3 = 28, kNgpDy4 = 32;
-constexpr int kNgpSlots = 34;
-
 template <int NE, bool BWD>
 struct NgpSeq {
   static constexpr int count = BWD ? ngp_total_count(NE) : ngp_fwd_count(NE);
@@ -69,15 +64,15 @@ __device__ __forceinline__ bf16x8 masked_by(const f32x16& acc, const bf16x8& ref
   return f;
 }
 
-// FUSED (backward only): the weight gradients are formed inside this kernel.  The model has 10 K parameters, so a
+// Backward: the weight gradients are formed inside the kernel.  The model has 10 K parameters, so a
 // workgroup can keep its share of dW in registers for the whole launch: the workgroups are persistent (one per CU,
 // groups of 8 tiles taken round-robin), and after every backward step the 8 waves put the layer's X and dy fragments
 // into an LDS staging area (the layout the split-K body of fused_chain.h reads: one 32-evaluation step per wave),
 // then every wave accumulates ONE 32x32 tile of that layer's dW over its share of the 8 steps (transposed
-// ds_read_b64_tr_b16 reads) and the tiles leave by fp32 atomics once, at the end of the launch.  This removes the
-// 34 KiB per tile of X / dy dumps (written and read back: 2.3 GB per step at 4096 rays) and the second launch.
+// ds_read_b64_tr_b16 reads) and the tiles leave once, at the end of the launch (plain stores).  This removes the
+// 34 KiB per tile of X / dy dumps (written and read back: 2.3 GB per step at 4096 rays) and a second launch.
 struct NgpWgradProblem {
-  int shape, x_slot0, y_slot0, do_bias, first_block, n_blocks;
+  int unused_[6];          // not read; keeps the kernel's argument layout
   int out_dim;             // columns of the Flax kernel (= valid dy features)
   unsigned w_lo, w_hi, b_lo, b_hi;  // float offsets of kernel / bias in the gradient vector (64-bit, split)
   int rb0, rb1, rb2, rb3;  // per X fragment: first kernel row ...
@@ -100,9 +95,8 @@ struct NgpWgradEpi {
     const int nv = f == 0 ? pb.rv0 : (f == 1 ? pb.rv1 : (f == 2 ? pb.rv2 : pb.rv3));
     return r16 < nv ? base + r16 : -1;
   }
-  static __device__ __forceinline__ int row_limit(const NgpWgradProblem&, int) { return 0x7FFFFFFF; }
 };
-// k-parts of the fused mode per weight-gradient problem (host table order: Dense_3, Dense_2, Dense_1, Dense_4,
+// k-parts of the backward per weight-gradient problem (host table order: Dense_3, Dense_2, Dense_1, Dense_4,
 // Dense_0): a layer with NT < 4 dW tiles is dealt to its four waves as NT tiles x 4 / NT parts of the group's 256
 // evaluations, and every part has its own row in the partial-sum buffer
 constexpr int kNgpMaxParts = 4;
@@ -141,35 +135,29 @@ __global__ __launch_bounds__(256) void ngp_wparts_reduce_kernel(const float* __r
   }
 }
 
-constexpr int kNgpStageStep = 8 * kFragBytes;                 // fused mode: staging bytes per wave (<= 8 fragments per layer)
-constexpr int kNgpGmaxOff = kNgpLds + kWaves * kNgpStageStep;    // fused mode: 8 running maxima per lane (32 B)
+constexpr int kNgpStageStep = 8 * kFragBytes;                 // backward: staging bytes per wave (<= 8 fragments per layer)
+constexpr int kNgpGmaxOff = kNgpLds + kWaves * kNgpStageStep;    // backward: 8 running maxima per lane (32 B)
 constexpr int kNgpFusedLds = kNgpGmaxOff + kThreads * 32;        // 129 KiB: one persistent workgroup per CU
 
 #ifdef LNRF_TIMELINE
 __device__ unsigned long long* g_ngp_timeline_buf = nullptr;  // 8 waves x 1024 stamps (debug build only)
 #endif
 
-template <int NE, bool BWD, bool FUSED = false>
+template <int NE, bool BWD>
 __global__ __launch_bounds__(kThreads) void ngp_mlp_kernel(
     const char* __restrict__ packed, const float* __restrict__ enc_t, const float* __restrict__ d_g, int lf,
     int64_t M, int64_t n_tiles, float* __restrict__ density, float* __restrict__ rgb,
-    const float* __restrict__ g_density, const float* __restrict__ g_rgb, char* __restrict__ scratch,
+    const float* __restrict__ g_density, const float* __restrict__ g_rgb, char* __restrict__ /* not read */,
     float* __restrict__ g_enc_t, float* __restrict__ lmax_parts = nullptr, NgpWgradArgs wargs = NgpWgradArgs{},
     float* __restrict__ wparts = nullptr, int pstride = 0, int64_t dense_off = 0) {
-  static_assert(!FUSED || BWD, "FUSED is a backward mode");
   // backward: running max |d loss / d enc| of the rows this lane writes, 8 slots (rows 4h + 8j + {0,1} / + {2,3} are
   // the two features of levels 2h + 4j / 2h + 4j + 1): the fixed-point scale of the scatter pass.  The persistent
-  // (FUSED) kernel keeps the slots in LDS (32 bytes per lane, its registers are full), reduces them once at the end
+  // kernel keeps the slots in LDS (32 bytes per lane, its registers are full), reduces them once at the end
   // and stores one row of 16 per workgroup — plain stores; ngp_level_max_kernel folds the rows.  (Same-address
   // global atomics retire at ~10 ns each: 256 workgroups x 16 of them at the end of the launch measured +30 us,
   // a wave reduction per group +35 us.)
   __shared__ unsigned s_lmax[16];
-  float gmax[(BWD && !FUSED) ? 8 : 1];
-  if constexpr (BWD && !FUSED) {
-#pragma unroll
-    for (int i = 0; i < 8; ++i) gmax[i] = 0.0f;
-  }
-  if constexpr (FUSED) {
+  if constexpr (BWD) {
     float4* gm = reinterpret_cast<float4*>(smem + kNgpGmaxOff + threadIdx.x * 32);
     gm[0] = gm[1] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
   }
@@ -183,13 +171,13 @@ __global__ __launch_bounds__(kThreads) void ngp_mlp_kernel(
     for (int i = tid; i < kNgpBiasFloats; i += kThreads) bias_l[i] = bias_g[i];
     if (tid < 16) s_lmax[tid] = 0u;
   }
-  // persistent accumulators of the fused mode.  The layers are dealt to the two halves of the workgroup so that a
+  // persistent accumulators of the backward.  The layers are dealt to the two halves of the workgroup so that a
   // wave carries at most three dW tiles (five would not fit next to the chain's fragments): waves 0-3 take
   // Dense_3 (slot 0), Dense_4 (slot 1), Dense_0 (slot 2); waves 4-7 take Dense_2 (slot 0), Dense_1 (slot 1).
   constexpr int kWSlots = 3;
-  f32x16 wacc[FUSED ? kWSlots : 1];
-  float wbias[FUSED ? kWSlots : 1];
-  if constexpr (FUSED) {
+  f32x16 wacc[BWD ? kWSlots : 1];
+  float wbias[BWD ? kWSlots : 1];
+  if constexpr (BWD) {
 #pragma unroll
     for (int i = 0; i < kWSlots; ++i) {
       wacc[i] = zero_acc();
@@ -197,7 +185,7 @@ __global__ __launch_bounds__(kThreads) void ngp_mlp_kernel(
     }
   }
   const int64_t n_groups = n_tiles / kWaves;
-  for (int64_t group = blockIdx.x; group < n_groups; group += FUSED ? (int64_t)gridDim.x : n_groups) {
+  for (int64_t group = blockIdx.x; group < n_groups; group += BWD ? (int64_t)gridDim.x : n_groups) {
   const int64_t tile = group * kWaves + wave;
   const int64_t m = tile * kTileCols + c;
   const bool valid = m < M;
@@ -206,11 +194,11 @@ __global__ __launch_bounds__(kThreads) void ngp_mlp_kernel(
 #ifdef LNRF_TIMELINE
   ring.tl.buf = g_ngp_timeline_buf;
   ring.tl.n = 0;
-  ring.tl.on = FUSED && NE == 2 && g_ngp_timeline_buf != nullptr && blockIdx.x == gridDim.x / 2 &&
+  ring.tl.on = BWD && NE == 2 && g_ngp_timeline_buf != nullptr && blockIdx.x == gridDim.x / 2 &&
                group == (int64_t)blockIdx.x + 2 * (int64_t)gridDim.x;
 #endif
   LNRF_TL_STAMP(ring);  // 0: group start
-  if constexpr (FUSED) __syncthreads();  // previous group's LDS reads (ring, staging) are finished
+  if constexpr (BWD) __syncthreads();  // previous group's LDS reads (ring, staging) are finished
   LNRF_TL_STAMP(ring);  // 1: after the top barrier
 
   // encoding fragments: k slot (ks, h, j) <-> feature 16 ks + 8 (j >> 2) + 4 h + (j & 3) (row of enc_t).
@@ -218,7 +206,7 @@ __global__ __launch_bounds__(kThreads) void ngp_mlp_kernel(
   // through an opaque copy so that the 16 row addresses are computed here instead of being hoisted out of the group
   // loop and spilled (that version waited for 32 scratch / global round trips in a row: 12 us of a 32 us group).
   int64_t Ms = M;
-  if constexpr (FUSED) asm volatile("" : "+s"(Ms));
+  if constexpr (BWD) asm volatile("" : "+s"(Ms));
   const int64_t mm = valid ? m : M - 1;
   float ev[NE][8];
   static_for<NE>([&](auto ks_) {
@@ -255,7 +243,7 @@ __global__ __launch_bounds__(kThreads) void ngp_mlp_kernel(
   LNRF_TL_STAMP(ring);  // 4: after the barrier
 
   const char* wstream = packed;
-  if constexpr (FUSED) asm volatile("" : "+s"(wstream));  // keep the stage addresses out of the group loop's preheader
+  if constexpr (BWD) asm volatile("" : "+s"(wstream));  // keep the stage addresses out of the group loop's preheader
   ring.stream = wstream;
   ring.wave = wave;
   ring.lane = lane;
@@ -281,11 +269,7 @@ __global__ __launch_bounds__(kThreads) void ngp_mlp_kernel(
     }
   });
 
-  DumpAddr dump{scratch, n_tiles, tile, c, h};
-  auto dump_frag = [&](int slot, const bf16x8& f) {
-    if (BWD && !FUSED) stream_store(dump.at(slot), frag_to_bits(f));  // unconditional: tiles are padded to whole workgroups
-  };
-  // fused mode: stage fragment f (X fragments first, then dy) of this wave's tile; weight-gradient step of layer P
+  // backward: stage fragment f (X fragments first, then dy) of this wave's tile; weight-gradient step of layer P
   char* stage = smem + kNgpLds + wave * kNgpStageStep;
   auto stage_frag = [&](int f, const bf16x8& v) {
     *reinterpret_cast<uint4*>(stage + f * kFragBytes + dump_lane_off(f, c, h)) = frag_to_bits(v);
@@ -383,23 +367,7 @@ __global__ __launch_bounds__(kThreads) void ngp_mlp_kernel(
     }
     return;
   } else {
-    // ---- backward: X dumps for the weight gradients
-    static_for<2>([&](auto i_) {
-      constexpr int i = decltype(i_)::value;
-      if constexpr (i < NE) dump_frag(kNgpXEnc + i, ef[i]);
-      else dump_frag(kNgpXEnc + i, zero_frag());
-    });
-    static_for<4>([&](auto i_) {
-      constexpr int i = decltype(i_)::value;
-      dump_frag(kNgpXH0 + i, h0[i]);
-      dump_frag(kNgpXC1 + i, c1[i]);
-      dump_frag(kNgpXC2 + i, c2[i]);
-    });
-    dump_frag(kNgpXCat + 0, de[0]);
-    dump_frag(kNgpXCat + 1, de[1]);
-    dump_frag(kNgpXCat + 2, o16);
-    dump_frag(kNgpXCat + 3, zero_frag());
-
+    // ---- backward
     // head gradients in fp32: tanh' and exp'
     bf16x8 dy4 = zero_frag();
     dy4[0] = (__bf16)(gy4[0] * (1.0f - y[0] * y[0]));
@@ -407,9 +375,7 @@ __global__ __launch_bounds__(kThreads) void ngp_mlp_kernel(
     dy4[2] = (__bf16)(gy4[2] * (1.0f - y[2] * y[2]));
     if (h != 0) dy4 = zero_frag();
     const float g_logit = h == 0 ? g_dens * dens : 0.0f;
-    dump_frag(kNgpDy4, dy4);
-    dump_frag(kNgpDy4 + 1, zero_frag());
-    if constexpr (FUSED) {  // Dense_4: X = c2, dy = dy4
+    {  // Dense_4: X = c2, dy = dy4
       static_for<4>([&](auto i_) { stage_frag(decltype(i_)::value, c2[decltype(i_)::value]); });
       stage_frag(4, dy4);
       stage_frag(5, zero_frag());
@@ -424,10 +390,8 @@ __global__ __launch_bounds__(kThreads) void ngp_mlp_kernel(
           constexpr int o = decltype(o_)::value;
           dy3[2 * o] = masked_by<0>(acc, c2[2 * o]);
           dy3[2 * o + 1] = masked_by<1>(acc, c2[2 * o + 1]);
-          dump_frag(kNgpDy3 + 2 * o, dy3[2 * o]);
-          dump_frag(kNgpDy3 + 2 * o + 1, dy3[2 * o + 1]);
         });
-    if constexpr (FUSED) {  // Dense_3: X = c1, dy = dy3
+    {  // Dense_3: X = c1, dy = dy3
       static_for<4>([&](auto i_) {
         stage_frag(decltype(i_)::value, c1[decltype(i_)::value]);
         stage_frag(4 + decltype(i_)::value, dy3[decltype(i_)::value]);
@@ -441,10 +405,8 @@ __global__ __launch_bounds__(kThreads) void ngp_mlp_kernel(
           constexpr int o = decltype(o_)::value;
           dy2[2 * o] = masked_by<0>(acc, c1[2 * o]);
           dy2[2 * o + 1] = masked_by<1>(acc, c1[2 * o + 1]);
-          dump_frag(kNgpDy2 + 2 * o, dy2[2 * o]);
-          dump_frag(kNgpDy2 + 2 * o + 1, dy2[2 * o + 1]);
         });
-    if constexpr (FUSED) {  // Dense_2: X = [d_emb, out] (24 + 16 features in 4 fragments), dy = dy2
+    {  // Dense_2: X = [d_emb, out] (24 + 16 features in 4 fragments), dy = dy2
       stage_frag(0, de[0]);
       stage_frag(1, de[1]);
       stage_frag(2, o16);
@@ -460,10 +422,8 @@ __global__ __launch_bounds__(kThreads) void ngp_mlp_kernel(
           f32x16 t = acc;
           t[0] += g_logit;
           dy1 = acc_to_frag<0, false>(t);
-          dump_frag(kNgpDy1, dy1);
-          dump_frag(kNgpDy1 + 1, zero_frag());
         });
-    if constexpr (FUSED) {  // Dense_1: X = h0, dy = dy1
+    {  // Dense_1: X = h0, dy = dy1
       static_for<4>([&](auto i_) { stage_frag(decltype(i_)::value, h0[decltype(i_)::value]); });
       stage_frag(4, dy1);
       stage_frag(5, zero_frag());
@@ -476,10 +436,8 @@ __global__ __launch_bounds__(kThreads) void ngp_mlp_kernel(
           constexpr int o = decltype(o_)::value;
           dy0[2 * o] = masked_by<0>(acc, h0[2 * o]);
           dy0[2 * o + 1] = masked_by<1>(acc, h0[2 * o + 1]);
-          dump_frag(kNgpDy0 + 2 * o, dy0[2 * o]);
-          dump_frag(kNgpDy0 + 2 * o + 1, dy0[2 * o + 1]);
         });
-    if constexpr (FUSED) {  // Dense_0: X = hash-grid encoding, dy = dy0
+    {  // Dense_0: X = hash-grid encoding, dy = dy0
       stage_frag(0, ef[0]);
       if constexpr (NE > 1) stage_frag(1, ef[1]);
       else stage_frag(1, zero_frag());
@@ -501,15 +459,10 @@ __global__ __launch_bounds__(kThreads) void ngp_mlp_kernel(
               tmax[q >> 1] = fmaxf(tmax[q >> 1], fabsf(acc[q]));
             }
           }
-          if constexpr (FUSED) {
-            float4* gm = reinterpret_cast<float4*>(smem + kNgpGmaxOff + tid * 32);
-            const float4 a = gm[0], b = gm[1];
-            gm[0] = make_float4(fmaxf(a.x, tmax[0]), fmaxf(a.y, tmax[1]), fmaxf(a.z, tmax[2]), fmaxf(a.w, tmax[3]));
-            gm[1] = make_float4(fmaxf(b.x, tmax[4]), fmaxf(b.y, tmax[5]), fmaxf(b.z, tmax[6]), fmaxf(b.w, tmax[7]));
-          } else {
-#pragma unroll
-            for (int i = 0; i < 8; ++i) gmax[i] = fmaxf(gmax[i], tmax[i]);
-          }
+          float4* gm = reinterpret_cast<float4*>(smem + kNgpGmaxOff + tid * 32);
+          const float4 a = gm[0], b = gm[1];
+          gm[0] = make_float4(fmaxf(a.x, tmax[0]), fmaxf(a.y, tmax[1]), fmaxf(a.z, tmax[2]), fmaxf(a.w, tmax[3]));
+          gm[1] = make_float4(fmaxf(b.x, tmax[4]), fmaxf(b.y, tmax[5]), fmaxf(b.z, tmax[6]), fmaxf(b.w, tmax[7]));
         });
   LNRF_TL_STAMP(ring);  // group end
   }
@@ -518,9 +471,7 @@ __global__ __launch_bounds__(kThreads) void ngp_mlp_kernel(
     if (lmax_parts) {  // kernel argument: uniform
 #pragma unroll
       for (int i = 0; i < 8; ++i) {
-        float v;
-        if constexpr (FUSED) v = reinterpret_cast<const float*>(smem + kNgpGmaxOff + tid * 32)[i];
-        else v = gmax[i];
+        float v = reinterpret_cast<const float*>(smem + kNgpGmaxOff + tid * 32)[i];
 #pragma unroll
         for (int o = 16; o >= 1; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
         // non-negative floats order like their bit patterns
@@ -529,8 +480,6 @@ __global__ __launch_bounds__(kThreads) void ngp_mlp_kernel(
       __syncthreads();
       if (tid < 16) lmax_parts[(int64_t)blockIdx.x * 16 + tid] = __uint_as_float(s_lmax[tid]);
     }
-  }
-  if constexpr (FUSED) {
     // The launch's share of dW: every wave stores its tile (and bias sums) ONCE, with plain stores, into the row of its
     // (workgroup, k-part) in `wparts`; ngp_wparts_reduce_kernel folds the rows into the gradient vector.  (fp32
     // atomics straight into the gradient — 256 workgroups hitting the same 10 K addresses — cost 76 us per launch,
@@ -586,25 +535,6 @@ __global__ __launch_bounds__(256) void ngp_level_max_kernel(const float* __restr
   __syncthreads();
   if ((int)threadIdx.x < n_levels && threadIdx.x < 16 && s_max[threadIdx.x] != 0u)
     atomicMax(&level_absmax[threadIdx.x], s_max[threadIdx.x]);
-}
-
-// ---------------------------------------------------------------------------------------------
-// weight gradients: the shared split-K body with InstantNGP addressing
-// ---------------------------------------------------------------------------------------------
-constexpr int kNgpWgSpi = 4;  // steps per barrier: 2 x 4 x 8 KiB = 64 KiB of LDS, two workgroups per CU
-constexpr int kNgpWgradLds = 2 * kNgpWgSpi * 8 * kFragBytes;
-
-__global__ __launch_bounds__(kThreads) void ngp_wgrad_kernel(NgpWgradArgs args, const char* __restrict__ scratch,
-                                                             int64_t n_tiles, float* __restrict__ grads) {
-  NgpWgradProblem pb = args.p[0];
-#pragma unroll
-  for (int i = 1; i < kNgpLayers; ++i)
-    if ((int)blockIdx.x >= args.p[i].first_block) pb = args.p[i];
-  switch (pb.shape) {
-    case 0: wgrad_body<2, 4, 1, 8, kNgpWgSpi, NgpWgradEpi>(pb, scratch, scratch, n_tiles, grads); break;
-    case 1: wgrad_body<4, 2, 2, 4, kNgpWgSpi, NgpWgradEpi>(pb, scratch, scratch, n_tiles, grads); break;
-    default: wgrad_body<4, 4, 2, 4, kNgpWgSpi, NgpWgradEpi>(pb, scratch, scratch, n_tiles, grads); break;
-  }
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -871,7 +801,7 @@ static bool ngp_supported(const lnrf_ngp_mlp_desc* d) {
   return d && d->hidden_dim == kNgpHidden && d->density_dim == kNgpDensityDim && d->density_layers == 1 &&
          d->color_layers == 2 && d->d_freqs == 4 && d->enc_dim >= 1 && d->enc_dim <= 32;
 }
-// padded to whole workgroups (8 waves) so that the dump stores need no branch (see tiles_for in nerf_mlp.hip)
+// padded to whole workgroups (8 waves): the kernels walk groups of 8 tiles
 static inline int64_t ngp_tiles(int64_t m) { return ((m + kTileCols - 1) / kTileCols + kWaves - 1) / kWaves * kWaves; }
 static NgpOffsets ngp_offsets(const lnrf_ngp_mlp_desc* d) {
   NgpOffsets o;
@@ -905,14 +835,8 @@ extern "C" int64_t lnrf_ngp_mlp_packed_bytes(const lnrf_ngp_mlp_desc* desc) {
 }
 static int64_t ngp_lmax_bytes(int64_t n_tiles) { return (n_tiles + kWaves - 1) / kWaves * 16 * (int64_t)sizeof(float); }
 
-// The two-launch backward (fragment dumps + split-K weight-gradient kernel with fp32 atomics) is the A/B partner of the
-// persistent backward; only experiment builds (common.h) can select it, with LNRF_NGP_WGRAD=split.
-static bool ngp_fused_wgrad_enabled() {
-  static const bool on = !exp_env_is("LNRF_NGP_WGRAD", 's');
-  return on;
-}
-// scratch = [partial dW rows of the persistent backward | (experiment builds: fragment dumps of the two-launch path)]
-// then one row of 16 per-level maxima per workgroup.  At most kNgpMaxPersistent workgroups form partial rows.
+// scratch = [partial dW rows of the persistent backward] then one row of 16 per-level maxima per workgroup.  At most
+// kNgpMaxPersistent workgroups form partial rows.
 constexpr int kNgpMaxPersistent = 512;
 static int ngp_dense_params(const lnrf_ngp_mlp_desc* d) {
   const NgpOffsets o = ngp_offsets(d);
@@ -922,11 +846,7 @@ static int ngp_pstride(const lnrf_ngp_mlp_desc* d) { return (ngp_dense_params(d)
 static int64_t ngp_lmax_off(const lnrf_ngp_mlp_desc* d, int64_t n_tiles) {
   int64_t rows = n_tiles / kWaves;
   if (rows > kNgpMaxPersistent) rows = kNgpMaxPersistent;
-  int64_t bytes = rows * kNgpMaxParts * ngp_pstride(d) * (int64_t)sizeof(float);
-  if (!ngp_fused_wgrad_enabled()) {
-    const int64_t dumps = (int64_t)kNgpSlots * n_tiles * kFragBytes;
-    if (dumps > bytes) bytes = dumps;
-  }
+  const int64_t bytes = rows * kNgpMaxParts * ngp_pstride(d) * (int64_t)sizeof(float);
   return (bytes + 255) / 256 * 256;
 }
 
@@ -1026,112 +946,73 @@ extern "C" int lnrf_ngp_mlp_bwd(const lnrf_ngp_mlp_desc* desc, const void* packe
   if (m == 0) return LNRF_OK;
   LNRF_CHECK_ARG(packed && enc_t && d && g_density && g_rgb && scratch && g_enc_t && grads, "null pointer");
   const int64_t n_tiles = ngp_tiles(m);
-  const dim3 grid((unsigned)((n_tiles + kWaves - 1) / kWaves)), block(kThreads);
   hipStream_t st = as_stream(stream);
   int rc;
-  // per-workgroup rows of level maxima live behind the dumps in the scratch buffer
+  // per-workgroup rows of level maxima live behind the partial dW rows in the scratch buffer
   float* lmax_parts = level_absmax ? reinterpret_cast<float*>(reinterpret_cast<char*>(scratch) +
                                                               ngp_lmax_off(desc, n_tiles))
                                    : nullptr;
   const int n_levels = desc->enc_dim / 2;
-  // weight-gradient problems (five Dense layers)
+  // weight-gradient problems (five Dense layers): where each kernel's rows and columns sit in the gradient vector
   const NgpOffsets off = ngp_offsets(desc);
   const int lf = desc->enc_dim;
   NgpWgradArgs a;
-  int first = 0;
-  auto add = [&](int i, int shape, int xs, int ys, int layer, int rb0, int rv0, int rb1, int rv1, int rb2, int rv2,
-                 int rb3, int rv3) {
-    NgpWgradProblem p;
-    p.shape = shape; p.x_slot0 = xs; p.y_slot0 = ys; p.do_bias = 1;
+  auto add = [&](int i, int layer, int rb0, int rv0, int rb1, int rv1, int rb2, int rv2, int rb3, int rv3) {
+    NgpWgradProblem p{};
     p.out_dim = ngp_out_dim(layer);
     p.w_lo = (unsigned)(off.w[layer] & 0xFFFFFFFFll); p.w_hi = (unsigned)(off.w[layer] >> 32);
     p.b_lo = (unsigned)(off.b[layer] & 0xFFFFFFFFll); p.b_hi = (unsigned)(off.b[layer] >> 32);
     p.rb0 = rb0; p.rv0 = rv0; p.rb1 = rb1; p.rv1 = rv1;
     p.rb2 = rb2; p.rv2 = rv2; p.rb3 = rb3; p.rv3 = rv3;
-    int64_t nb = 102;  // 5 problems x 102 = 510 workgroups = two per CU
-    const int64_t max_nb = (n_tiles + 2 * kNgpWgSpi - 1) / (2 * kNgpWgSpi);
-    if (nb > max_nb) nb = max_nb;
-    p.first_block = first;
-    p.n_blocks = (int)nb;
-    first += (int)nb;
     a.p[i] = p;
   };
-  add(0, 2, kNgpXC1, kNgpDy3, 3, 0, 16, 16, 16, 32, 16, 48, 16);
-  add(1, 2, kNgpXCat, kNgpDy2, 2, 0, 16, 16, 8, kNgpDembDim, 16, 0, 0);
-  add(2, 1, kNgpXH0, kNgpDy1, 1, 0, 16, 16, 16, 32, 16, 48, 16);
-  add(3, 1, kNgpXC2, kNgpDy4, 4, 0, 16, 16, 16, 32, 16, 48, 16);
-  add(4, 0, kNgpXEnc, kNgpDy0, 0, 0, lf < 16 ? lf : 16, 16, lf > 16 ? lf - 16 : 0, 0, 0, 0, 0);
-  if (ngp_fused_wgrad_enabled()) {
-    // one persistent workgroup per CU forms the weight gradients itself (no dumps, no second launch)
-    int dev = 0, cus = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e == hipSuccess) e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    if (e != hipSuccess) return hip_fail(e, "hipDeviceGetAttribute(multiprocessor count)");
-    int64_t nb = n_tiles / kWaves;
-    if (nb > cus) nb = cus;
-    if (nb > kNgpMaxPersistent) nb = kNgpMaxPersistent;
-    const dim3 pgrid((unsigned)nb);
-    // partial dW rows (workgroup, k-part) live where the two-launch path keeps its dumps: nb <= n_tiles / 8 rows of
-    // 4 x pstride floats against 8 x 34 KiB of dump room per workgroup
-    NgpPartsPlan plan;
-    for (int i = 0; i < kNgpLayers; ++i) {
-      const int layer = i == 0 ? 3 : (i == 1 ? 2 : (i == 2 ? 1 : (i == 3 ? 4 : 0)));  // problem i of the table above
-      plan.lo[i] = (int)(off.w[layer] - desc->dense_offset);
-      plan.hi[i] = (int)(off.b[layer] - desc->dense_offset) + ngp_out_dim(layer);
-      plan.parts[i] = ngp_wgrad_parts(i);
-    }
-    const int n_params = ngp_dense_params(desc);
-    const int pstride = ngp_pstride(desc);
-    float* wparts = reinterpret_cast<float*>(scratch);
-    if (desc->enc_dim <= 16) {
-      rc = ngp_ensure_lds(ngp_mlp_kernel<1, true, true>, kNgpFusedLds);
-      if (rc) return rc;
-      hipLaunchKernelGGL((ngp_mlp_kernel<1, true, true>), pgrid, block, kNgpFusedLds, st, (const char*)packed, enc_t, d,
-                         (int)desc->enc_dim, m, n_tiles, nullptr, nullptr, g_density, g_rgb, nullptr, g_enc_t,
-                         lmax_parts, a, wparts, pstride, (int64_t)desc->dense_offset);
-    } else {
-      rc = ngp_ensure_lds(ngp_mlp_kernel<2, true, true>, kNgpFusedLds);
-      if (rc) return rc;
-      hipLaunchKernelGGL((ngp_mlp_kernel<2, true, true>), pgrid, block, kNgpFusedLds, st, (const char*)packed, enc_t, d,
-                         (int)desc->enc_dim, m, n_tiles, nullptr, nullptr, g_density, g_rgb, nullptr, g_enc_t,
-                         lmax_parts, a, wparts, pstride, (int64_t)desc->dense_offset);
-    }
-    LNRF_LAUNCH_CHECK();
-    hipLaunchKernelGGL(ngp_wparts_reduce_kernel, dim3((unsigned)((n_params + 31) / 32)), dim3(256), 0, st, wparts,
-                       (int)nb, pstride, n_params, plan, grads + desc->dense_offset);
-    LNRF_LAUNCH_CHECK();
-    if (lmax_parts) {
-      hipLaunchKernelGGL(ngp_level_max_kernel, dim3(1), dim3(256), 0, st, lmax_parts, (int)nb, n_levels,
-                         reinterpret_cast<unsigned*>(level_absmax));
-      LNRF_LAUNCH_CHECK();
-    }
-    return LNRF_OK;
+  add(0, 3, 0, 16, 16, 16, 32, 16, 48, 16);
+  add(1, 2, 0, 16, 16, 8, kNgpDembDim, 16, 0, 0);
+  add(2, 1, 0, 16, 16, 16, 32, 16, 48, 16);
+  add(3, 4, 0, 16, 16, 16, 32, 16, 48, 16);
+  add(4, 0, 0, lf < 16 ? lf : 16, 16, lf > 16 ? lf - 16 : 0, 0, 0, 0, 0);
+  // one persistent workgroup per CU forms the weight gradients itself (no dumps, no second launch)
+  int dev = 0, cus = 0;
+  hipError_t e = hipGetDevice(&dev);
+  if (e == hipSuccess) e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+  if (e != hipSuccess) return hip_fail(e, "hipDeviceGetAttribute(multiprocessor count)");
+  int64_t nb = n_tiles / kWaves;
+  if (nb > cus) nb = cus;
+  if (nb > kNgpMaxPersistent) nb = kNgpMaxPersistent;
+  const dim3 pgrid((unsigned)nb), block(kThreads);
+  // partial dW rows (workgroup, k-part) at the front of the scratch buffer
+  NgpPartsPlan plan;
+  for (int i = 0; i < kNgpLayers; ++i) {
+    const int layer = i == 0 ? 3 : (i == 1 ? 2 : (i == 2 ? 1 : (i == 3 ? 4 : 0)));  // problem i of the table above
+    plan.lo[i] = (int)(off.w[layer] - desc->dense_offset);
+    plan.hi[i] = (int)(off.b[layer] - desc->dense_offset) + ngp_out_dim(layer);
+    plan.parts[i] = ngp_wgrad_parts(i);
   }
+  const int n_params = ngp_dense_params(desc);
+  const int pstride = ngp_pstride(desc);
+  float* wparts = reinterpret_cast<float*>(scratch);
   if (desc->enc_dim <= 16) {
-    rc = ngp_ensure_lds(ngp_mlp_kernel<1, true>, kNgpLds);
+    rc = ngp_ensure_lds(ngp_mlp_kernel<1, true>, kNgpFusedLds);
     if (rc) return rc;
-    hipLaunchKernelGGL((ngp_mlp_kernel<1, true>), grid, block, kNgpLds, st, (const char*)packed, enc_t, d,
-                       (int)desc->enc_dim, m, n_tiles, nullptr, nullptr, g_density, g_rgb, (char*)scratch, g_enc_t,
-                       lmax_parts);
+    hipLaunchKernelGGL((ngp_mlp_kernel<1, true>), pgrid, block, kNgpFusedLds, st, (const char*)packed, enc_t, d,
+                       (int)desc->enc_dim, m, n_tiles, nullptr, nullptr, g_density, g_rgb, nullptr, g_enc_t,
+                       lmax_parts, a, wparts, pstride, (int64_t)desc->dense_offset);
   } else {
-    rc = ngp_ensure_lds(ngp_mlp_kernel<2, true>, kNgpLds);
+    rc = ngp_ensure_lds(ngp_mlp_kernel<2, true>, kNgpFusedLds);
     if (rc) return rc;
-    hipLaunchKernelGGL((ngp_mlp_kernel<2, true>), grid, block, kNgpLds, st, (const char*)packed, enc_t, d,
-                       (int)desc->enc_dim, m, n_tiles, nullptr, nullptr, g_density, g_rgb, (char*)scratch, g_enc_t,
-                       lmax_parts);
+    hipLaunchKernelGGL((ngp_mlp_kernel<2, true>), pgrid, block, kNgpFusedLds, st, (const char*)packed, enc_t, d,
+                       (int)desc->enc_dim, m, n_tiles, nullptr, nullptr, g_density, g_rgb, nullptr, g_enc_t,
+                       lmax_parts, a, wparts, pstride, (int64_t)desc->dense_offset);
   }
   LNRF_LAUNCH_CHECK();
+  hipLaunchKernelGGL(ngp_wparts_reduce_kernel, dim3((unsigned)((n_params + 31) / 32)), dim3(256), 0, st, wparts,
+                     (int)nb, pstride, n_params, plan, grads + desc->dense_offset);
+  LNRF_LAUNCH_CHECK();
   if (lmax_parts) {
-    hipLaunchKernelGGL(ngp_level_max_kernel, dim3(1), dim3(256), 0, st, lmax_parts, (int)grid.x, n_levels,
+    hipLaunchKernelGGL(ngp_level_max_kernel, dim3(1), dim3(256), 0, st, lmax_parts, (int)nb, n_levels,
                        reinterpret_cast<unsigned*>(level_absmax));
     LNRF_LAUNCH_CHECK();
   }
-
-  rc = ngp_ensure_lds(ngp_wgrad_kernel, kNgpWgradLds);
-  if (rc) return rc;
-  hipLaunchKernelGGL(ngp_wgrad_kernel, dim3((unsigned)first), dim3(kThreads), kNgpWgradLds, st, a,
-                     (const char*)scratch, n_tiles, grads);
-  LNRF_LAUNCH_CHECK();
   return LNRF_OK;
 }
 

@@ -1048,7 +1048,7 @@ extern "C" int lnrf_refnerf_normal_pass(const void* packed, const void* save, co
 // the nine weight-gradient problems of the trunk: Dense_1..8 (hidden x hidden) and x_emb x [dy0 | dy5] (Dense_0 and the
 // x_emb rows of Dense_5: the two dumps are neighbours, nerf_layout.h); 256 workgroups = one per CU (two rounds of 512 cost
 // twice the partial-sum traffic for the same streaming rate)
-// `slabs`: room for 512 workgroups' partial sums (kSlabBlockBytes each) — the deterministic epilogue of fused_chain.h
+// `slabs`: room for 512 workgroups' partial sums (kSlabBlockBytes each) — the slab epilogue of fused_chain.h
 static int trunk_wgrad(const void* xbuf, const void* ybuf, int64_t n_tiles, int do_bias, float* grads, hipStream_t st,
                        float* slabs) {
   WgradArgs a;
@@ -1069,8 +1069,7 @@ static int trunk_wgrad(const void* xbuf, const void* ybuf, int64_t n_tiles, int 
   };
   for (int l = 1; l <= 8; ++l) add(0, kSaveH + (l - 1) * 16, grad_dy_slot(l), l, ROW_HIDDEN, 0, do_bias, 28, COL_256);
   add(7, kSaveXin, grad_dy_slot(0), 0, ROW_XEMB, 0, do_bias, 32, COL_DY0_DY5);
-  return launch_nerf_wgrad(a, first, xbuf, ybuf, n_tiles, grads, st, WgLayout{kSaveTileSlots, kGradTileSlots},
-                           first <= 512 ? slabs : nullptr);
+  return launch_nerf_wgrad(a, first, xbuf, ybuf, n_tiles, grads, st, WgLayout{kSaveTileSlots, kGradTileSlots}, slabs);
 }
 // the slab region behind a gradient dump that was sized by lnrf_nerf_bwd_scratch_bytes
 static float* slabs_behind_dump(const void* dump, int64_t n_tiles) {
@@ -1182,5 +1181,5 @@ extern "C" int lnrf_refnerf_dir_bwd(const void* packed, const void* dsave, const
   add(4, kDirSaveH, kDirGradDy10, 3, kDirHidden, kDirW10, kDirB10, 56);
   float* slabs = reinterpret_cast<float*>(reinterpret_cast<char*>(scratch) + (int64_t)kDirGradSlots * n_tiles * kFragBytes);
   return launch_nerf_wgrad(a, first, dsave, scratch, n_tiles, grads, as_stream(stream),
-                           WgLayout{kDirSaveTileSlots, kDirGradTileSlots}, first <= 512 ? slabs : nullptr);
+                           WgLayout{kDirSaveTileSlots, kDirGradTileSlots}, slabs);
 }

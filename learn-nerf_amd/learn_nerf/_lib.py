@@ -53,8 +53,6 @@ PROTOTYPES = {
     "lnrf_termination_probs": (c_int32, [_P, _P, _P, _P, c_int64, c_int32, _P, _P]),
     "lnrf_composite_fwd": (c_int32, [_P, c_int64, _P, _P, _P, _P, _P, _P, _P, c_int32, _P, c_int64, c_int32,
                                      _P, _P, _P, _P, _P, c_int64, _P, _P]),
-    "lnrf_composite_bwd": (c_int32, [_P, _P, _P, _P, _P, _P, _P, c_int32, _P, c_int64, c_int32, _P, _P, _P,
-                                     c_int64, c_float, _F3, _P, _P, _P, _P, _P]),
     "lnrf_composite_bwd_scratch_bytes": (c_int64, [c_int64]),
     "lnrf_composite_bwd_det": (c_int32, [_P, _P, _P, _P, _P, _P, _P, c_int32, _P, c_int64, c_int32, _P, _P, _P,
                                          c_int64, c_float, _F3, _P, _P, _P, _P, _P, c_int64, _P]),
@@ -62,7 +60,6 @@ PROTOTYPES = {
     "lnrf_dense_fwd": (c_int32, [_P, c_int64, _P, _P, c_int32, _P, c_int64, c_int64, c_int32, c_int32, _P]),
     "lnrf_act_bwd": (c_int32, [_P, c_int64, _P, c_int64, c_int32, c_int64, c_int32, _P]),
     "lnrf_dense_bwd_input": (c_int32, [_P, c_int64, _P, _P, c_int64, c_int32, c_int64, c_int32, c_int32, _P]),
-    "lnrf_dense_bwd_weight": (c_int32, [_P, c_int64, _P, c_int64, _P, _P, c_int64, c_int32, c_int32, _P]),
     "lnrf_gemm_f32_det_scratch_bytes": (c_int64, [c_int64, c_int32, c_int64]),
     "lnrf_gemm_f32_det": (c_int32, [_P, c_int64, c_int64, _P, c_int64, c_int64, _P, c_int64, c_int32, c_int64, _P, c_int64, _P]),
     "lnrf_dense_bwd_weight_scratch_bytes": (c_int64, [c_int64, c_int32, c_int32]),
@@ -70,7 +67,6 @@ PROTOTYPES = {
     "lnrf_gemm_f32": (c_int32, [_P, c_int64, c_int64, _P, c_int64, c_int64, _P, c_int64, _P, c_int32, c_int32,
                                 c_int64, c_int32, c_int64, c_int32, _P]),
     "lnrf_hashgrid_fwd": (c_int32, [POINTER(HashGridDesc), _P, _P, c_int64, _P, _P]),
-    "lnrf_hashgrid_bwd": (c_int32, [POINTER(HashGridDesc), _P, c_int64, _P, _P, _P]),
     "lnrf_hashgrid_bwd_scratch_bytes": (c_int64, [POINTER(HashGridDesc), c_int64]),
     "lnrf_hashgrid_bwd_bucketed": (c_int32, [POINTER(HashGridDesc), _P, _P, c_int64, _P, _P, _P, _P, c_int64, _P]),
     "lnrf_hashgrid_jvp": (c_int32, [POINTER(HashGridDesc), _P, _P, _P, c_int64, _P, _P]),
@@ -113,7 +109,6 @@ PROTOTYPES = {
     "lnrf_nerf_pack_weights_split": (c_int32, [POINTER(NerfShape), _P, _P, _P]),
     "lnrf_nerf_mlp_fwd_split": (c_int32, [POINTER(NerfShape), _P, _P, _P, _P, c_int64, _P, c_int32, c_int64, _P, _P,
                                           _P]),
-    "lnrf_nerf_mlp_bwd": (c_int32, [POINTER(NerfShape), _P, _P, _P, _P, _P, _P, c_int64, _P, _P, _P]),
     "lnrf_nerf_mlp_bwd_chain": (c_int32, [POINTER(NerfShape), _P, _P, _P, _P, _P, _P, c_int64, _P, _P]),
     "lnrf_nerf_mlp_bwd_weights": (c_int32, [POINTER(NerfShape), _P, _P, c_int64, _P, _P]),
     "lnrf_nerf_bwd_ls_scratch_bytes": (c_int64, [POINTER(NerfShape), c_int64]),

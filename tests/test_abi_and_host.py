@@ -22,7 +22,8 @@ def header_symbols():
     return sorted(set(re.findall(r"\b(lnrf_[a-z0-9_]+)\s*\(", text)))
 
 
-def test_library_exports_every_header_symbol():
+def test_library_exports_every_header_symbol_of_0_2():
+    """Header, ctypes prototypes and library agree, at C-ABI version 0.2.0 (LNRF_VERSION 200)."""
     from learn_nerf import _lib
 
     lib = _lib.lib()  # raises if the .so is missing: build() must have run
@@ -32,7 +33,7 @@ def test_library_exports_every_header_symbol():
         assert hasattr(lib, name), f"liblnrf.so does not export {name}"
         assert name in _lib.PROTOTYPES, f"no ctypes prototype for {name}"
     assert set(_lib.PROTOTYPES) == set(syms), "prototype table and header disagree"
-    assert lib.lnrf_version() == 100
+    assert lib.lnrf_version() == 200
 
 
 def test_size_queries_without_gpu():

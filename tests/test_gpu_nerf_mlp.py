@@ -226,8 +226,8 @@ def test_fused_bf16_backward(m):
 def test_backward_is_bit_reproducible(m):
     """The weight-gradient launch leaves its partial sums as slabs that a second launch folds in a fixed order
     (fused_chain.h, slab epilogue), so two backward passes over the same inputs give bit-identical gradients — which
-    fp32 atomics (LNRF_WGRAD_ATOMICS=1, the older epilogue) do not.  Kernel and bias gradients, ragged and multi-workgroup
-    sizes."""
+    an epilogue of fp32 atomics (whose arrival order varies from run to run) would not.  Kernel and bias gradients, ragged
+    and multi-workgroup sizes."""
     model, _, flat = make_model("bf16")
     x, d, gen = make_points(m, seed=3)
     g_dens = torch.randn(m, generator=gen).float().cuda()

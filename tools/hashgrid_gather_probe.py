@@ -1,5 +1,6 @@
 """Times lnrf_hashgrid_fwd at BASELINE configs[2] size (786,432 evaluations, L = 16, T = 2^19) and at the coarse size
-(262,144, L = 6).  LNRF_HASHGRID_LDS=0 disables the LDS-staged path of the 16^3 levels."""
+(262,144, L = 6).  The 16^3 levels take the LDS-staged path (measured neutral against the direct gather,
+whose switch has been removed)."""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "learn-nerf_amd")); sys.path.insert(0, ROOT)
@@ -19,4 +20,4 @@ for levels, m in ((16, 786432), (6, 262144)):
         enc.encode_t(tables, x)
     e1.record(); torch.cuda.synchronize()
     ms = e0.elapsed_time(e1) / 20
-    print(f"L={levels} m={m} LDS={os.environ.get('LNRF_HASHGRID_LDS', '1')}: {ms:.4f} ms = {m * levels * 64 / ms / 1e6:.0f} GB/s algorithmic")
+    print(f"L={levels} m={m}: {ms:.4f} ms = {m * levels * 64 / ms / 1e6:.0f} GB/s algorithmic")
