@@ -277,3 +277,21 @@ def test_pan_and_spin_camera_paths():
     assert np.abs(np.array(spun[1].camera_direction) - np.array([-1.0, 0.0, 0.0])).max() < 1e-12
     assert all(v.camera_origin == base.camera_origin and v.y_axis == base.y_axis and v.x_fov == 0.5 for v in spun)
     assert base.x_axis == (1.0, 0.0, 0.0)  # the input view is not modified
+
+
+def test_poison_helper_reviews_every_lease_purpose():
+    """tests/gpu_poison.py poisons only the workspace purposes it lists as holding values (never indices).  Every purpose
+    the package leases must be in one of its two tables, so that a new or renamed purpose is reviewed for index content
+    instead of being silently skipped (or poisoned) by the workspace-poisoning GPU tests."""
+    import gpu_poison
+
+    pkg = os.path.join(ROOT, "learn-nerf_amd", "learn_nerf")
+    used = set()
+    for name in os.listdir(pkg):
+        if name.endswith(".py"):
+            used |= set(re.findall(r"_ws\.lease\(\s*\"([a-z0-9_]+)\"", open(os.path.join(pkg, name)).read()))
+    reviewed = set(gpu_poison.POISONED_PURPOSES) | set(gpu_poison.UNPOISONED_PURPOSES)
+    assert {"nerf_save", "nerf_bwd_ls", "nerf_bwd", "hashgrid_bwd"} <= used
+    assert used <= reviewed, f"lease purposes not reviewed in gpu_poison.py: {sorted(used - reviewed)}"
+    assert not set(gpu_poison.POISONED_PURPOSES) & set(gpu_poison.UNPOISONED_PURPOSES)
+    assert "hashgrid_bwd" in gpu_poison.UNPOISONED_PURPOSES
