@@ -529,6 +529,25 @@ int lnrf_step_log(float* sums, float inv_count, float grad_scale, int32_t clear,
 /* *out += sum x^2 (tree_norm numerator, train.py:92-97). out must be zeroed by the caller. */
 int lnrf_sq_norm(const float* x, int64_t n, float* out, lnrf_stream_t stream);
 
+/* ------------------------------------------------------------------ mesh ---- */
+
+/* Marching cubes over a volume (scripts/marching_cubes.py:62-66: skimage.measure.marching_cubes of the padded occupancy
+ * grid at the threshold), in two passes with one read-back of the two counts between them.  vol: fp32 [nx, ny, nz]
+ * in C order, every dimension >= 2; a point is inside when v > level (NaN is outside).  Vertex, face and edge
+ * conventions: the header comment of csrc/mesh.hip.  Output order is deterministic (no atomics).
+ * scratch: lnrf_mc_scratch_bytes bytes, 16-byte aligned (-1 for a dimension < 2). */
+int64_t lnrf_mc_scratch_bytes(int64_t nx, int64_t ny, int64_t nz);
+/* pass 1: per-point codes and per-tile counts, scanned; counts (device int64 [2]): [0] = vertices V, [1] = faces F. */
+int lnrf_mc_count(const float* vol, int64_t nx, int64_t ny, int64_t nz, float level, void* scratch, int64_t* counts,
+                  lnrf_stream_t stream);
+/* pass 2, from the scratch of an lnrf_mc_count of the same volume and level and its counts n_verts = V, n_faces = F
+ * (host values): verts [V, 3] (fp32, index space) and faces [F, 3] (int32, outward); nothing is written at or beyond
+ * V or F.  LNRF_ERR_SHAPE when V or F does not fit in int32.  verts / faces may be NULL when V / F is 0. */
+int lnrf_mc_emit(const float* vol, int64_t nx, int64_t ny, int64_t nz, float level, const void* scratch,
+                 int64_t n_verts, int64_t n_faces, float* verts, int32_t* faces, lnrf_stream_t stream);
+/* (host) the compile-time case table: out[256 * 16] int8, triangles as triples of edge numbers, -1 terminated. */
+int lnrf_mc_case_table(int8_t* out);
+
 #ifdef __cplusplus
 }
 #endif

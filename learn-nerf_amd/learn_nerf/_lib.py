@@ -141,6 +141,10 @@ PROTOTYPES = {
                                        c_float, _P, _P]),
     "lnrf_step_log": (c_int32, [_P, c_float, c_float, c_int32, _P, _P]),
     "lnrf_sq_norm": (c_int32, [_P, c_int64, _P, _P]),
+    "lnrf_mc_scratch_bytes": (c_int64, [c_int64, c_int64, c_int64]),
+    "lnrf_mc_count": (c_int32, [_P, c_int64, c_int64, c_int64, c_float, _P, _P, _P]),
+    "lnrf_mc_emit": (c_int32, [_P, c_int64, c_int64, c_int64, c_float, _P, c_int64, c_int64, _P, _P, _P]),
+    "lnrf_mc_case_table": (c_int32, [_P]),
 }
 
 _lib = None
