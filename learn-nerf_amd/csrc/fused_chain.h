@@ -6,7 +6,7 @@
 
 #include "common.h"
 #include "fast_math.h"
-#include "nerf_layout.h"
+#include "nerf_wgrad.h"
 
 namespace lnrf {
 using namespace nl;
@@ -26,9 +26,7 @@ __device__ __forceinline__ void static_for(F&& f) {
   static_for_impl(f, std::make_integer_sequence<int, N>{});
 }
 
-constexpr int kWaves = 8;            // waves per workgroup
 constexpr int kThreads = kWaves * 64;
-constexpr int kTileCols = 32;        // evaluations per wave
 constexpr int kStageBytes = kStageFrags * kFragBytes;  // 16 KiB
 constexpr int kSlots = 3;            // LDS stages: being read, published-next, being written
 constexpr int kRingBytes = kSlots * kStageBytes;
@@ -397,12 +395,6 @@ struct WgStage {
   }
 };
 
-// slab epilogue of wgrad_body: floats per (workgroup, wave): up to 9 accumulator tiles of 64 lanes x 16 + 4 bias rows
-constexpr int kSlabMaxTiles = 9, kSlabMaxTO = 4;
-constexpr int kSlabTileFloats = 64 * 16;
-constexpr int kSlabWaveFloats = kSlabMaxTiles * kSlabTileFloats + kSlabMaxTO * 64;
-constexpr int64_t kSlabBlockBytes = (int64_t)kWaves * kSlabWaveFloats * (int64_t)sizeof(float);
-
 // PB supplies x_slot0, y_slot0, first_block, n_blocks.  The partial sums go to `slabs`; wgrad_reduce_tile() maps them
 // to gradient-vector offsets.
 template <int NXF, int NYF, int WI, int WO, int SPI, bool PLAIN, class PB>
@@ -546,21 +538,17 @@ constexpr int kSlabReduceWaves = 4;  // 8 measured no faster (finish phase 0.67 
 template <int NXF, int NYF, int WI, int WO, class EPI, class PB>
 __device__ __forceinline__ void wgrad_reduce_tile(const PB& pb, int w, int j, const float* __restrict__ slabs,
                                                   float* __restrict__ grads, float* lds) {
-  constexpr int NI = NXF / 2, NO = NYF / 2;
-  constexpr int TI = (NI + WI - 1) / WI, TO = (NO + WO - 1) / WO;
-  static_assert(TI * TO <= kSlabMaxTiles && TO <= kSlabMaxTO, "slab layout");
-  if (j >= TI * TO) return;  // uniform for the workgroup
+  if (j >= kWgradWaveTiles<NXF, NYF, WI, WO>) return;  // uniform for the workgroup
   const int lane = threadIdx.x & 63, q = threadIdx.x >> 6;
-  const int a = j / TO, b = j % TO;
-  const int wi = w / WO, wo = w % WO;
-  const int it = wi + WI * a, ot = wo + WO * b;
-  if (it >= NI || ot >= NO) return;
+  const WgradTile tile = wgrad_tile<NXF, NYF, WI, WO>(w, j);
+  if (!tile.real) return;
+  const int b = tile.b;
   const float* __restrict__ src = slabs + ((int64_t)pb.first_block * kWaves + w) * kSlabWaveFloats;
   const int64_t blk_stride = (int64_t)kWaves * kSlabWaveFloats;
   float acc[16];
 #pragma unroll
   for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
-  const bool bias = wi == 0 && a == 0 && pb.do_bias;
+  const bool bias = tile.bias && pb.do_bias;
   float bsum = 0.0f;
   constexpr int U = 4;  // slabs in flight per wave
   for (int s0 = q; s0 < pb.n_blocks; s0 += U * kSlabReduceWaves) {
@@ -604,21 +592,17 @@ __device__ __forceinline__ void wgrad_reduce_tile(const PB& pb, int w, int j, co
     bsum += lds[(p * 17 + 16) * 64 + lane];
   }
   const int colr = lane & 31, hh = lane >> 5;
-  int out_idx = -1, out_dim = 1;
-  int64_t w_off = 0, b_off = 0;
-  EPI::cols(pb, ot, colr, out_idx, out_dim, w_off, b_off);
-  const int row_lim = EPI::row_limit(pb, ot);
+  const WgradOwner<EPI, PB> own(pb, tile.ot, colr);
   if (bias) {
     float sacc = bsum;
     sacc += __shfl_xor(sacc, 32, 64);
-    if (hh == 0 && out_idx >= 0 && b_off >= 0) grads[b_off + out_idx] += sacc;
+    int64_t bi;
+    if (own.bias(hh, bi)) grads[bi] += sacc;
   }
 #pragma unroll
   for (int qq = 0; qq < 16; ++qq) {
-    const int r = (qq & 3) + 8 * (qq >> 2) + 4 * hh;  // row in the 32-feature tile
-    const int f = 2 * it + (r >> 4);                   // k-step slot within X
-    const int in_idx = EPI::row(pb, f, r & 15);
-    if (out_idx >= 0 && in_idx >= 0 && in_idx < row_lim) grads[w_off + (int64_t)in_idx * out_dim + out_idx] += acc[qq];
+    int64_t wi;
+    if (own.weight(pb, tile.it, hh, qq, wi)) grads[wi] += acc[qq];
   }
 }
 

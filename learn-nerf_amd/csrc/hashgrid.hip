@@ -708,9 +708,8 @@ extern "C" int lnrf_hashgrid_jvp(const lnrf_hashgrid_desc* desc, const float* ta
       if (d.table_size[staged.level[i]] > max_rows) max_rows = d.table_size[staged.level[i]];
     int64_t bx = (m + 1023) / 1024;
     if (bx > 1024) bx = 1024;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(hashgrid_fwd_kernel<true>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, kStageEntries * 8);
-    if (e != hipSuccess) return hip_fail(e, "hipFuncSetAttribute(max dynamic LDS)");
+    rc = set_max_dynamic_lds(hashgrid_fwd_kernel<true>, kStageEntries * 8);
+    if (rc) return rc;
     hipLaunchKernelGGL(hashgrid_fwd_kernel<true>, dim3((unsigned)bx, (unsigned)staged.n), dim3(512), max_rows * 8,
                        as_stream(stream), d, staged, tables, x, u, m, enc_t);
     LNRF_LAUNCH_CHECK();

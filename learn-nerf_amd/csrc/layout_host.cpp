@@ -1,12 +1,45 @@
 // layout_host.cpp — host build of the index maps of the fused NeRF kernels (nerf_layout.h) and of the
 // positional-encoding sincos (fast_math.h), so that tests/test_nerf_layout.py can run the exact packing /
-// fragment logic on the CPU (no GPU needed) with an MFMA emulator.
+// fragment logic on the CPU (no GPU needed) with an MFMA emulator; and of the weight-gradient problem lists and their
+// gradient-vector addressing (nerf_wgrad.h).
 #include <stdint.h>
 
 #include "fast_math.h"
-#include "nerf_layout.h"
+#include "nerf_wgrad.h"
 
-using namespace lnrf::nl;
+using namespace lnrf;
+
+// ---- weight-gradient problem lists (nerf_wgrad.h).  which: 0 split backward, 1 layer-stationary finish phase,
+// 2 Ref-NeRF trunk, 3 Ref-NeRF normal backward, 4 Ref-NeRF directional block
+static WgradList wgrad_list_of(int which, int64_t n_tiles) {
+  return which == 0 ? wgrad_list_split(n_tiles) : which == 1 ? wgrad_list_ls_finish(n_tiles)
+       : which == 2 ? wgrad_list_ref_trunk(n_tiles) : which == 3 ? wgrad_list_ref_normal(n_tiles)
+                                                                 : wgrad_list_ref_dir(n_tiles);
+}
+// Walks what the fold of the list's launch walks (problem, wave, accumulator tile, lane, register and bias sum) and adds 1
+// to count[i] for every gradient-vector entry i it would add to; returns how many of them fall outside [0, n).
+template <int NXF, int NYF, int WI, int WO>
+static int64_t wgrad_count_owners(const WgradProblem& pb, int32_t* count, int64_t n) {
+  int64_t outside = 0;
+  int64_t i;
+  auto hit = [&](bool owned) {
+    if (!owned) return;
+    if (i >= 0 && i < n) ++count[i];
+    else ++outside;
+  };
+  for (int w = 0; w < kWaves; ++w)
+    for (int j = 0; j < kWgradWaveTiles<NXF, NYF, WI, WO>; ++j) {
+      const WgradTile tile = wgrad_tile<NXF, NYF, WI, WO>(w, j);
+      if (!tile.real) continue;
+      for (int lane = 0; lane < 64; ++lane) {
+        const int colr = lane & 31, hh = lane >> 5;
+        const WgradOwner<NerfWgradEpi, WgradProblem> own(pb, tile.ot, colr);
+        if (tile.bias && pb.do_bias) hit(own.bias(hh, i));
+        for (int qq = 0; qq < 16; ++qq) hit(own.weight(pb, tile.it, hh, qq, i));
+      }
+    }
+  return outside;
+}
 
 extern "C" {
 int lnrf_host_fwd_frags(void) { return kFwdFrags; }
@@ -70,4 +103,48 @@ int lnrf_host_grad_slot(int what, int arg) {
 int lnrf_host_demb_feat(int ks, int h, int j) { return demb_feat(ks, h, j); }
 int lnrf_host_dump_lane_off(int slot, int c, int hh) { return dump_lane_off(slot, c, hh); }
 void lnrf_host_sincos_pe(float r, float* s, float* c) { lnrf::sincos_pe(r, s, c); }
+
+// ---- weight-gradient problem lists: `which` as for wgrad_list_of ----
+// what 0 slab capacity of a launch (workgroups), 1 / 2 accumulator tiles / bias rows a slab has room for per wave,
+// 3 parameters of a NeRFModel, 4..7 kDirW9, kDirB9, kDirW10, kDirB10
+int lnrf_host_wgrad_const(int what) {
+  const int v[8] = {kWgradMaxBlocks, kSlabMaxTiles, kSlabMaxTO, kParamCount, kDirW9, kDirB9, kDirW10, kDirB10};
+  return v[what];
+}
+// out[6 i ..]: first_block, n_blocks, TI * TO, TO, do_bias, 1 if nerf_ls_fold_kernel carries the shape; returns the
+// number of problems, -1 for a shape outside the table
+int lnrf_host_wgrad_list(int which, int64_t n_tiles, int32_t* out) {
+  const WgradList list = wgrad_list_of(which, n_tiles);
+  for (int i = 0; i < list.args.n_problems; ++i) {
+    const WgradProblem& pb = list.args.p[i];
+    int32_t* o = out + 6 * i;
+    o[0] = pb.first_block; o[1] = pb.n_blocks; o[4] = pb.do_bias; o[5] = 0;
+    switch (pb.shape) {
+#define X(name, id, NXF, NYF, WI, WO, SPI) case name: o[2] = WgShape<name>::TI * WgShape<name>::TO; o[3] = WgShape<name>::TO; break;
+      LNRF_WGRAD_SHAPES(X, X)
+#undef X
+      default: return -1;
+    }
+    switch (pb.shape) {
+#define X(name) case name:
+      LNRF_WGRAD_LS_SHAPES(X, X) o[5] = 1; break;
+#undef X
+      default: break;
+    }
+  }
+  return list.args.n_problems;
+}
+int64_t lnrf_host_wgrad_owners(int which, int64_t n_tiles, int32_t* count, int64_t n) {
+  const WgradList list = wgrad_list_of(which, n_tiles);
+  int64_t outside = 0;
+  for (int i = 0; i < list.args.n_problems; ++i) {
+    const WgradProblem& pb = list.args.p[i];
+    switch (pb.shape) {
+#define X(name, id, NXF, NYF, WI, WO, SPI) case name: outside += wgrad_count_owners<NXF, NYF, WI, WO>(pb, count, n); break;
+      LNRF_WGRAD_SHAPES(X, X)
+#undef X
+    }
+  }
+  return outside;
+}
 }

@@ -485,17 +485,21 @@ __global__ __launch_bounds__(64 * kSlabReduceWaves) void nerf_ls_fold_kernel(LsF
   if (bid < n_small) {
     const int prob = bid / (kWaves * kSlabMaxTiles), w = bid / kSlabMaxTiles % kWaves, j = bid % kSlabMaxTiles;
     const WgradProblem pb = a.w[k].p[prob];
-    switch (pb.shape) {  // the shapes ls_backward() launches
-      case 7: wgrad_reduce_tile<4, 32, 2, 4, NerfWgradEpi>(pb, w, j, a.small_slabs[k], a.grads[k], lds); break;
-      case 6: wgrad_reduce_tile<18, 10, 4, 2, NerfWgradEpi>(pb, w, j, a.small_slabs[k], a.grads[k], lds); break;
-      default: wgrad_reduce_tile<8, 2, 4, 2, NerfWgradEpi>(pb, w, j, a.small_slabs[k], a.grads[k], lds); break;
+    switch (pb.shape) {
+#define X(name)                                                                                                    \
+  case name:                                                                                                       \
+    wgrad_reduce_tile<WgShape<name>::NXF, WgShape<name>::NYF, WgShape<name>::WI, WgShape<name>::WO, NerfWgradEpi>( \
+        pb, w, j, a.small_slabs[k], a.grads[k], lds);                                                              \
+    break;
+      LNRF_WGRAD_LS_SHAPES(X, default: X)
+#undef X
     }
   } else if (bid - n_small < kLsStages * 64) {
     ls_fold_block<kSlabReduceWaves>(bid - n_small, a.ls_slabs[k], a.pipelines[k], a.grads[k], lds);
   }
 }
 
-// ---- head: the chain truncated after dz (flags 0 and 1 of nerf_chain.h) -----------------------------------------
+// ---- head: the chain truncated after dz (HEAD_ONLY of nerf_chain.h) ------------------------------------------------
 struct BwdHeadSeq {
   static constexpr int count = bwd_cons_base(2);  // 76 fragments: Dense_11^T and [Dense_10 | Dense_9]^T
   static constexpr int at(int c) { return bwd_seq(c); }
@@ -516,8 +520,8 @@ __global__ __launch_bounds__(kThreads) void nerf_bwd_head_kernel(
   ring.stream = packed + kPackBwdOff;
   ring.wave = wave;
   ring.lane = lane;
-  GlobalDumpSink sink{DumpAddr{gdump, n_tiles, tile, lane & 31, lane >> 5, kGradTileSlots}};
-  bwd_chain_tile<GlobalDumpSink, decltype(ring), true>(ring, sink, save, n_tiles, density, rgb, g_density, g_rgb, M, tile, lane);
+  const DumpAddr gd{gdump, n_tiles, tile, lane & 31, lane >> 5, kGradTileSlots};
+  bwd_chain_tile<true>(ring, gd, save, n_tiles, density, rgb, g_density, g_rgb, M, tile, lane);
 }
 
 }  // namespace lnrf
@@ -532,75 +536,72 @@ extern "C" int lnrf_debug_set_ls_timeline(void* buf) {
 }
 #endif
 
-static int ls_pipelines_for_device(int* out) {
+constexpr int kLsMaxPipelines = 64;
+// pipelines of a launch (one per 8 CUs), at least `need`
+static int ls_pipelines_for_device(int need, int* out) {
   int dev = 0, cus = 0;
   hipError_t e = hipGetDevice(&dev);
   if (e == hipSuccess) e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
   if (e != hipSuccess) return hip_fail(e, "hipDeviceGetAttribute(multiprocessor count)");
-  *out = cus / kLsStages;
+  *out = cus / kLsStages < kLsMaxPipelines ? cus / kLsStages : kLsMaxPipelines;
+  if (*out < need) {
+    set_error("layer-stationary backward: the device has too few CUs for a pipeline of 8 per model");
+    return LNRF_ERR_UNSUPPORTED;
+  }
   return LNRF_OK;
 }
-constexpr int kLsMaxPipelines = 64;
-static int64_t ls_dump_bytes(int64_t m) { return (int64_t)kGradSlots * nerf_tiles_for(m) * kFragBytes; }
-// workgroups of the three small problems (x_emb x [dy0 | dy5], [z | d_emb] x dy10m, h10 x dy11), in proportion to the bytes
-// they stream per tile (36, 28, 10 KiB)
-static int ls_small_blocks(int i) {
-  const int share[3] = {36, 28, 10};
-  return 256 * share[i] / 74;
+
+// `scratch` of one model, in bytes from its start: the gradient dump | the slabs of the small problems | the hand-off
+// counters, one 128-byte line per (pipeline, stage), and behind them the status word | the slabs of the pipelines
+constexpr int64_t kLsCounterWords = (int64_t)kLsMaxPipelines * kLsStages * kLsCounterStride;
+constexpr int64_t kLsCounterBytes = (kLsCounterWords + 64) * (int64_t)sizeof(unsigned);
+struct LsScratch {
+  int64_t small_slabs, counters, status, ls_slabs, bytes;
+};
+static LsScratch ls_scratch(int64_t m) {
+  LsScratch s;
+  s.small_slabs = (int64_t)kGradSlots * padded_tiles(m) * kFragBytes;
+  s.counters = s.small_slabs + kWgradSlabBytes;
+  s.status = s.counters + kLsCounterWords * (int64_t)sizeof(unsigned);
+  s.ls_slabs = s.counters + kLsCounterBytes;
+  s.bytes = s.ls_slabs + (int64_t)kLsMaxPipelines * kLsStages * kLsSlabBlockBytes;
+  return s;
 }
-static int64_t ls_small_slab_bytes() { return 512 * kSlabBlockBytes; }
-static int64_t ls_counter_bytes() { return ((int64_t)kLsMaxPipelines * kLsStages * kLsCounterStride + 64) * (int64_t)sizeof(unsigned); }
+static LsJob ls_job(const void* packed, const void* save, void* scratch, int64_t m, int pipelines) {
+  const LsScratch at = ls_scratch(m);
+  char* sc = (char*)scratch;
+  return LsJob{(const char*)packed, (const char*)save, sc, reinterpret_cast<unsigned*>(sc + at.counters),
+               reinterpret_cast<float*>(sc + at.ls_slabs), reinterpret_cast<unsigned*>(sc + at.status), padded_tiles(m),
+               pipelines};
+}
 
 extern "C" int64_t lnrf_nerf_bwd_ls_scratch_bytes(const lnrf_nerf_shape* s, int64_t m) {
-  if (!nerf_shape_fused(s)) return -1;
-  return lnrf::ls_scratch_bytes(m);
+  return nerf_shape_fused(s) ? ls_scratch(m).bytes : -1;
 }
-
-int64_t lnrf::ls_scratch_bytes(int64_t m) {
-  return ls_dump_bytes(m) + ls_small_slab_bytes() + ls_counter_bytes() + (int64_t)kLsMaxPipelines * kLsStages * kLsSlabBlockBytes;
+extern "C" int64_t lnrf_nerf_bwd_ls_status_offset(const lnrf_nerf_shape* s, int64_t m) {
+  return nerf_shape_fused(s) ? ls_scratch(m).status : -1;
 }
-int64_t lnrf::ls_small_slab_off(int64_t m) { return ls_dump_bytes(m); }
+int64_t lnrf::ls_scratch_bytes(int64_t m) { return ls_scratch(m).bytes; }
+float* lnrf::ls_small_slabs(void* scratch, int64_t m) {
+  return reinterpret_cast<float*>((char*)scratch + ls_scratch(m).small_slabs);
+}
 
 int lnrf::launch_ls_pipeline(const void* packed, const void* save, void* scratch, int64_t m, float* grads, hipStream_t st) {
   int total = 0;
-  int rc = ls_pipelines_for_device(&total);
+  int rc = ls_pipelines_for_device(1, &total);
+  if (!rc) rc = set_max_dynamic_lds(nerf_bwd_ls_kernel, kLsLds);
   if (rc) return rc;
-  if (total > kLsMaxPipelines) total = kLsMaxPipelines;
-  if (total < 1) {
-    set_error("layer-stationary backward: the device has fewer than 8 CUs");
-    return LNRF_ERR_UNSUPPORTED;
-  }
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(nerf_bwd_ls_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, kLsLds);
-  if (e != hipSuccess) return hip_fail(e, "hipFuncSetAttribute(max dynamic LDS)");
-  const int64_t n_tiles = nerf_tiles_for(m);
-  char* sc = (char*)scratch;
-  unsigned* counters = reinterpret_cast<unsigned*>(sc + ls_dump_bytes(m) + ls_small_slab_bytes());
-  float* slabs = reinterpret_cast<float*>(sc + ls_dump_bytes(m) + ls_small_slab_bytes() + ls_counter_bytes());
-  e = hipMemsetAsync(counters, 0, ls_counter_bytes(), st);
-  if (e != hipSuccess) return hip_fail(e, "hipMemsetAsync(counters)");
   LsArgs a;
   a.n_jobs = 1;
   a.total_pipelines = total;
-  LsJob& j = a.job[0];
-  j.packed = (const char*)packed;
-  j.save = (const char*)save;
-  j.gdump = sc;
-  j.counters = counters;
-  j.slabs = slabs;
-  j.status = counters + (int64_t)kLsMaxPipelines * kLsStages * kLsCounterStride;
-  j.n_tiles = n_tiles;
-  j.pipelines = total;
-  a.job[1] = a.job[0];
+  a.job[0] = a.job[1] = ls_job(packed, save, scratch, m, total);
+  hipError_t e = hipMemsetAsync(a.job[0].counters, 0, kLsCounterBytes, st);
+  if (e != hipSuccess) return hip_fail(e, "hipMemsetAsync(counters)");
   hipLaunchKernelGGL(nerf_bwd_ls_kernel, dim3((unsigned)(total * kLsStages)), dim3(kLsThreads), kLsLds, st, a);
   LNRF_LAUNCH_CHECK();
-  hipLaunchKernelGGL(nerf_ls_reduce_kernel, dim3(kLsStages * 64), dim3(256), 0, st, (const float*)slabs, total, grads);
+  hipLaunchKernelGGL(nerf_ls_reduce_kernel, dim3(kLsStages * 64), dim3(256), 0, st, (const float*)a.job[0].slabs, total, grads);
   LNRF_LAUNCH_CHECK();
   return LNRF_OK;
-}
-
-extern "C" int64_t lnrf_nerf_bwd_ls_status_offset(const lnrf_nerf_shape* s, int64_t m) {
-  if (!nerf_shape_fused(s)) return -1;
-  return ls_dump_bytes(m) + ls_small_slab_bytes() + (int64_t)kLsMaxPipelines * kLsStages * kLsCounterStride * (int64_t)sizeof(unsigned);
 }
 
 namespace {
@@ -616,14 +617,12 @@ struct LsModel {
 
 // head launch + pipeline launch (one or two models) + small problems + reduce launches
 static int ls_backward(const LsModel* mdl, int n_models, int phases, hipStream_t st) {
+  constexpr int kHeadLds = kRingBytes + round_up(kBiasFloats * 4, 1024);
   int total = 0;
-  int rc = ls_pipelines_for_device(&total);
+  int rc = ls_pipelines_for_device(n_models, &total);
+  if (!rc) rc = set_max_dynamic_lds(nerf_bwd_head_kernel, kHeadLds);
+  if (!rc) rc = set_max_dynamic_lds(nerf_bwd_ls_kernel, kLsLds);
   if (rc) return rc;
-  if (total > kLsMaxPipelines) total = kLsMaxPipelines;
-  if (total < n_models) {
-    set_error("lnrf_nerf_mlp_bwd_ls: the device has too few CUs for a pipeline per model");
-    return LNRF_ERR_UNSUPPORTED;
-  }
   // pipelines proportional to the evaluations of each model
   int pipes[2] = {total, 0};
   if (n_models == 2) {
@@ -636,94 +635,52 @@ static int ls_backward(const LsModel* mdl, int n_models, int phases, hipStream_t
   LsArgs a;
   a.n_jobs = n_models;
   a.total_pipelines = total;
-  rc = [&]() -> int {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(nerf_bwd_head_kernel),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, kRingBytes + round_up(kBiasFloats * 4, 1024));
-    if (e == hipSuccess)
-      e = hipFuncSetAttribute(reinterpret_cast<const void*>(nerf_bwd_ls_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, kLsLds);
-    return e == hipSuccess ? LNRF_OK : hip_fail(e, "hipFuncSetAttribute(max dynamic LDS)");
-  }();
-  if (rc) return rc;
   for (int k = 0; k < n_models; ++k) {
     const LsModel& md = mdl[k];
-    const int64_t n_tiles = nerf_tiles_for(md.m);
-    char* sc = (char*)md.scratch;
-    unsigned* counters = reinterpret_cast<unsigned*>(sc + ls_dump_bytes(md.m) + ls_small_slab_bytes());
-    float* slabs = reinterpret_cast<float*>(sc + ls_dump_bytes(md.m) + ls_small_slab_bytes() + ls_counter_bytes());
+    const LsJob& j = a.job[k] = ls_job(md.packed, md.save, md.scratch, md.m, pipes[k]);
     if (phases & 1) {
-      hipLaunchKernelGGL(nerf_bwd_head_kernel, dim3((unsigned)(n_tiles / kWaves)), dim3(kThreads),
-                         kRingBytes + round_up(kBiasFloats * 4, 1024), st, (const char*)md.packed, (const char*)md.save,
-                         md.density, md.rgb, md.g_density, md.g_rgb, md.m, n_tiles, sc, counters,
-                         (phases & 2) ? (int)(ls_counter_bytes() / sizeof(unsigned)) : 0);
+      hipLaunchKernelGGL(nerf_bwd_head_kernel, dim3((unsigned)(j.n_tiles / kWaves)), dim3(kThreads), kHeadLds, st, j.packed,
+                         j.save, md.density, md.rgb, md.g_density, md.g_rgb, md.m, j.n_tiles, j.gdump, j.counters,
+                         (phases & 2) ? (int)(kLsCounterBytes / sizeof(unsigned)) : 0);
       LNRF_LAUNCH_CHECK();
     }
     if ((phases & 3) == 2) {  // pipeline phase on its own (bench sections): nobody cleared the counters yet
-      hipError_t e = hipMemsetAsync(counters, 0, ls_counter_bytes(), st);
+      hipError_t e = hipMemsetAsync(j.counters, 0, kLsCounterBytes, st);
       if (e != hipSuccess) return hip_fail(e, "hipMemsetAsync(counters)");
     }
-    LsJob& j = a.job[k];
-    j.packed = (const char*)md.packed;
-    j.save = (const char*)md.save;
-    j.gdump = sc;
-    j.counters = counters;
-    j.slabs = slabs;
-    j.status = counters + (int64_t)kLsMaxPipelines * kLsStages * kLsCounterStride;
-    j.n_tiles = n_tiles;
-    j.pipelines = pipes[k];
   }
   if (n_models == 1) a.job[1] = a.job[0];
   if (phases & 2) {
     hipLaunchKernelGGL(nerf_bwd_ls_kernel, dim3((unsigned)(total * kLsStages)), dim3(kLsThreads), kLsLds, st, a);
     LNRF_LAUNCH_CHECK();
   }
+  if (!(phases & 4)) return LNRF_OK;
   LsFoldArgs fold;
-  for (int k = 0; k < n_models && (phases & 4); ++k) {
+  for (int k = 0; k < n_models; ++k) {
     const LsModel& md = mdl[k];
-    const int64_t n_tiles = nerf_tiles_for(md.m);
-    // the five problems that are not a pipeline stage, fed by the dumps the two launches above left behind
-    WgradArgs w;
-    w.n_problems = 0;
-    int first = 0;
-    const int64_t cap = (n_tiles + 5) / 6;
-    auto add = [&](int nb_want, int shape, int xs, int ys, int dense, int row_map, int row_off, int col_map, int do_bias) {
-      WgradProblem p;
-      p.shape = shape; p.x_slot0 = xs; p.y_slot0 = ys; p.dense = dense; p.row_map = row_map; p.row_off = row_off;
-      p.col_map = col_map; p.do_bias = do_bias;
-      p.w_off = p.b_off = p.out_dim = p.n_rows = 0;
-      int64_t nb = nb_want;
-      if (nb > cap) nb = cap;
-      if (nb < 1) nb = 1;
-      p.first_block = first;
-      p.n_blocks = (int)nb;
-      first += (int)nb;
-      w.p[w.n_problems++] = p;
-    };
-    // workgroups in proportion to the bytes a problem streams per tile (36, 28, 10 KiB): 256 = one per CU (384 = one and a half rounds is 10 % slower, 512 equal within the box-to-box spread).
-    // [z | d_emb] and [dy0 | dy5] are neighbours in the save / dump layouts (nerf_layout.h), so dy10m and x_emb are read once.
-    add(ls_small_blocks(0), 7, kSaveXin, grad_dy_slot(0), 0, ROW_XEMB, 0, COL_DY0_DY5, 1);   // Dense_0 and Dense_5 rows 256..315
-    add(ls_small_blocks(1), 6, kSaveZ, kGradDy10m, 10, ROW_Z_DEMB, 0, COL_DY10M, 1);         // Dense_10 (all 280 rows) and Dense_9
-    add(ls_small_blocks(2), 4, kSaveH10, kGradDy11, 11, ROW_HIDDEN, 0, COL_DY11, 1);          // Dense_11
-    float* small_slabs = reinterpret_cast<float*>((char*)md.scratch + ls_dump_bytes(md.m));
+    const LsJob& j = a.job[k];
+    // the problems that are not a pipeline stage, fed by the dumps the two launches above left behind
+    const WgradList w = wgrad_list_ls_finish(j.n_tiles);
+    float* small_slabs = ls_small_slabs(md.scratch, md.m);
     // interleaved walk: at any moment the 256 workgroups read neighbouring tiles (one 80 MB window moving through the save
     // and the dump) instead of 256 places 1/256 of the buffers apart — measured 0.60 vs 0.68 ms for the finish phase
-    rc = launch_nerf_wgrad(w, first, md.save, md.scratch, n_tiles, md.grads, st, WgLayout{kSaveTileSlots, kGradTileSlots, 1},
+    rc = launch_nerf_wgrad(w, md.save, md.scratch, j.n_tiles, md.grads, st, WgLayout{kSaveTileSlots, kGradTileSlots, 1},
                            small_slabs, false, false);
     if (rc) return rc;
-    fold.w[k] = w;
+    fold.w[k] = w.args;
     fold.small_slabs[k] = small_slabs;
-    fold.ls_slabs[k] = a.job[k].slabs;
+    fold.ls_slabs[k] = j.slabs;
     fold.grads[k] = md.grads;
     fold.pipelines[k] = pipes[k];
   }
-  if (phases & 4) {  // one fold launch for everything both models left in slabs
-    if (n_models == 1) {
-      fold.w[1] = fold.w[0]; fold.small_slabs[1] = fold.small_slabs[0]; fold.ls_slabs[1] = fold.ls_slabs[0];
-      fold.grads[1] = fold.grads[0]; fold.pipelines[1] = fold.pipelines[0];
-    }
-    const int gx = fold.w[0].n_problems * kWaves * kSlabMaxTiles + kLsStages * 64;  // both models have the same problems
-    hipLaunchKernelGGL(nerf_ls_fold_kernel, dim3((unsigned)gx, (unsigned)n_models), dim3(64 * kSlabReduceWaves), 0, st, fold);
-    LNRF_LAUNCH_CHECK();
+  if (n_models == 1) {
+    fold.w[1] = fold.w[0]; fold.small_slabs[1] = fold.small_slabs[0]; fold.ls_slabs[1] = fold.ls_slabs[0];
+    fold.grads[1] = fold.grads[0]; fold.pipelines[1] = fold.pipelines[0];
   }
+  // one fold launch for everything both models left in slabs; both models have the same problems
+  const int gx = fold.w[0].n_problems * kWaves * kSlabMaxTiles + kLsStages * 64;
+  hipLaunchKernelGGL(nerf_ls_fold_kernel, dim3((unsigned)gx, (unsigned)n_models), dim3(64 * kSlabReduceWaves), 0, st, fold);
+  LNRF_LAUNCH_CHECK();
   return LNRF_OK;
 }
 
@@ -731,10 +688,7 @@ extern "C" int lnrf_nerf_mlp_bwd_ls(const lnrf_nerf_shape* shape, const void* pa
                                     const float* density, const float* rgb, const float* g_density,
                                     const float* g_rgb, int64_t m, void* scratch, float* grads, int32_t phases,
                                     lnrf_stream_t stream) {
-  if (!nerf_shape_fused(shape)) {
-    set_error("lnrf_nerf_mlp_bwd_ls: only the default NeRFModel shape {5,4,256,128,10,4} is fused");
-    return LNRF_ERR_UNSUPPORTED;
-  }
+  LNRF_REQUIRE_NERF_SHAPE(shape);
   LNRF_CHECK_ARG(packed && save && density && rgb && g_density && g_rgb && scratch && grads, "null pointer");
   LNRF_CHECK_ARG(m >= 0, "bad m");
   if (m == 0) return LNRF_OK;
@@ -749,10 +703,7 @@ extern "C" int lnrf_nerf_mlp_bwd_ls2(const lnrf_nerf_shape* shape, const void* p
                                      const void* packed_b, const void* save_b, const float* density_b,
                                      const float* rgb_b, const float* g_density_b, const float* g_rgb_b, int64_t m_b,
                                      void* scratch_b, float* grads_b, int32_t phases, lnrf_stream_t stream) {
-  if (!nerf_shape_fused(shape)) {
-    set_error("lnrf_nerf_mlp_bwd_ls2: only the default NeRFModel shape {5,4,256,128,10,4} is fused");
-    return LNRF_ERR_UNSUPPORTED;
-  }
+  LNRF_REQUIRE_NERF_SHAPE(shape);
   LNRF_CHECK_ARG(packed_a && save_a && density_a && rgb_a && g_density_a && g_rgb_a && scratch_a && grads_a, "null pointer");
   LNRF_CHECK_ARG(packed_b && save_b && density_b && rgb_b && g_density_b && g_rgb_b && scratch_b && grads_b, "null pointer");
   LNRF_CHECK_ARG(m_a > 0 && m_b > 0, "both models need evaluations (use lnrf_nerf_mlp_bwd_ls for one)");

@@ -28,6 +28,8 @@ namespace nl {
 
 constexpr int kFragBytes = 1024;
 constexpr int kStageFrags = 16;  // frags consumed between two workgroup barriers
+constexpr int kTileCols = 32;    // evaluations per wave
+constexpr int kWaves = 8;        // waves per workgroup
 
 // ---- Flax parameter vector (Dense_i.kernel[in,out] row-major, then Dense_i.bias) ----------
 constexpr int kNumDense = 12;

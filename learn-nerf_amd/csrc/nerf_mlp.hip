@@ -398,8 +398,8 @@ __global__ __launch_bounds__(kThreads) void nerf_bwd_chain_kernel(
   ring.tl.on = g_timeline_buf != nullptr && blockIdx.x == gridDim.x / 2;
   ring.tl.stamp();
 #endif
-  GlobalDumpSink sink{DumpAddr{gdump, n_tiles, tile, lane & 31, lane >> 5, kGradTileSlots}};
-  bwd_chain_tile(ring, sink, save, n_tiles, density, rgb, g_density, g_rgb, M, tile, lane);
+  const DumpAddr gd{gdump, n_tiles, tile, lane & 31, lane >> 5, kGradTileSlots};
+  bwd_chain_tile(ring, gd, save, n_tiles, density, rgb, g_density, g_rgb, M, tile, lane);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -422,15 +422,10 @@ __global__ __launch_bounds__(kThreads) void nerf_wgrad_kernel(WgradArgs args, co
   for (int i = 1; i < kMaxProblems; ++i)
     if (i < args.n_problems && (int)blockIdx.x >= args.p[i].first_block) pb = args.p[i];
   switch (pb.shape) {
-    // steps per barrier chosen so that every body keeps ~60 KB of loads in flight per workgroup
-    case 0: wgrad_body<16, 16, 4, 2, 2, PLAIN>(pb, save, gdump, n_tiles, lay, slabs); break;
-    case 1: wgrad_body<16, 10, 4, 2, 2, PLAIN>(pb, save, gdump, n_tiles, lay, slabs); break;
-    case 2: wgrad_body<4, 16, 2, 4, 3, PLAIN>(pb, save, gdump, n_tiles, lay, slabs); break;
-    case 3: wgrad_body<2, 10, 1, 8, 5, PLAIN>(pb, save, gdump, n_tiles, lay, slabs); break;
-    case 5: wgrad_body<18, 8, 4, 2, 2, PLAIN>(pb, save, gdump, n_tiles, lay, slabs); break;  // Ref-NeRF Dense_9
-    case 6: wgrad_body<18, 10, 4, 2, 2, PLAIN>(pb, save, gdump, n_tiles, lay, slabs); break;  // [z | d_emb] x dy10m
-    case 7: wgrad_body<4, 32, 2, 4, 2, PLAIN>(pb, save, gdump, n_tiles, lay, slabs); break;   // x_emb x [dy0 | dy5]
-    default: wgrad_body<8, 2, 4, 2, 6, PLAIN>(pb, save, gdump, n_tiles, lay, slabs); break;
+#define X(name, id, NXF, NYF, WI, WO, SPI) \
+  case name: wgrad_body<NXF, NYF, WI, WO, SPI, PLAIN>(pb, save, gdump, n_tiles, lay, slabs); break;
+    LNRF_WGRAD_SHAPES(X, default: X)
+#undef X
   }
 }
 
@@ -441,15 +436,11 @@ __global__ __launch_bounds__(64 * kSlabReduceWaves) void nerf_wgrad_reduce_kerne
   __shared__ float lds[(kSlabReduceWaves - 1) * 17 * 64];
   const int prob = blockIdx.x / (kWaves * kSlabMaxTiles), w = blockIdx.x / kSlabMaxTiles % kWaves, j = blockIdx.x % kSlabMaxTiles;
   const WgradProblem pb = args.p[prob];
-  switch (pb.shape) {  // the shapes of nerf_wgrad_kernel
-    case 0: wgrad_reduce_tile<16, 16, 4, 2, NerfWgradEpi>(pb, w, j, slabs, grads, lds); break;
-    case 1: wgrad_reduce_tile<16, 10, 4, 2, NerfWgradEpi>(pb, w, j, slabs, grads, lds); break;
-    case 2: wgrad_reduce_tile<4, 16, 2, 4, NerfWgradEpi>(pb, w, j, slabs, grads, lds); break;
-    case 3: wgrad_reduce_tile<2, 10, 1, 8, NerfWgradEpi>(pb, w, j, slabs, grads, lds); break;
-    case 5: wgrad_reduce_tile<18, 8, 4, 2, NerfWgradEpi>(pb, w, j, slabs, grads, lds); break;
-    case 6: wgrad_reduce_tile<18, 10, 4, 2, NerfWgradEpi>(pb, w, j, slabs, grads, lds); break;
-    case 7: wgrad_reduce_tile<4, 32, 2, 4, NerfWgradEpi>(pb, w, j, slabs, grads, lds); break;
-    default: wgrad_reduce_tile<8, 2, 4, 2, NerfWgradEpi>(pb, w, j, slabs, grads, lds); break;
+  switch (pb.shape) {
+#define X(name, id, NXF, NYF, WI, WO, SPI) \
+  case name: wgrad_reduce_tile<NXF, NYF, WI, WO, NerfWgradEpi>(pb, w, j, slabs, grads, lds); break;
+    LNRF_WGRAD_SHAPES(X, default: X)
+#undef X
   }
 }
 
@@ -530,9 +521,6 @@ __global__ void nerf_pack_split_kernel(const float* __restrict__ params, char* _
 
 using namespace lnrf;
 
-static bool shape_supported(const lnrf_nerf_shape* s) { return nerf_shape_fused(s); }
-static inline int64_t tiles_for(int64_t m) { return nerf_tiles_for(m); }
-
 extern "C" int64_t lnrf_nerf_param_count(const lnrf_nerf_shape* s) {
   if (!s) return -1;
   const int64_t xe = 6 * s->x_freqs, de = 6 * s->d_freqs, hd = s->hidden_dim, cd = s->color_layer_dim;
@@ -546,60 +534,42 @@ extern "C" int64_t lnrf_nerf_param_count(const lnrf_nerf_shape* s) {
   return n;
 }
 extern "C" int64_t lnrf_nerf_packed_bytes(const lnrf_nerf_shape* s) {
-  return shape_supported(s) ? kPackBytes : -1;
+  return nerf_shape_fused(s) ? kPackBytes : -1;
 }
 extern "C" int64_t lnrf_nerf_save_bytes(const lnrf_nerf_shape* s, int64_t m) {
-  return shape_supported(s) ? (int64_t)kSaveSlots * tiles_for(m) * kFragBytes : -1;
+  return nerf_shape_fused(s) ? (int64_t)kSaveSlots * padded_tiles(m) * kFragBytes : -1;
 }
-// workgroups of one NeRFModel weight-gradient launch (sum of the per-problem counts in lnrf_nerf_mlp_bwd_weights), and
-// the most any launch_nerf_wgrad call may use: every caller's slab region holds this many slabs
-constexpr int kNerfWgradBlocks = 512;
-static int64_t grad_dump_bytes(int64_t m) { return (int64_t)kGradSlots * tiles_for(m) * kFragBytes; }
+static int64_t grad_dump_bytes(int64_t m) { return (int64_t)kGradSlots * padded_tiles(m) * kFragBytes; }
 extern "C" int64_t lnrf_nerf_bwd_scratch_bytes(const lnrf_nerf_shape* s, int64_t m) {
-  // the dy dump, then the partial-sum slabs of the weight-gradient launch (fused_chain.h, slab epilogue)
-  return shape_supported(s) ? grad_dump_bytes(m) + kNerfWgradBlocks * kSlabBlockBytes : -1;
+  // the dy dump, then the partial-sum slabs of the weight-gradient launch (nerf_wgrad.h)
+  return nerf_shape_fused(s) ? grad_dump_bytes(m) + kWgradSlabBytes : -1;
 }
 
 extern "C" int lnrf_nerf_pack_weights(const lnrf_nerf_shape* shape, const float* params, void* packed,
                                       lnrf_stream_t stream) {
-  if (!shape_supported(shape)) {
-    set_error("lnrf_nerf_pack_weights: only the default NeRFModel shape {5,4,256,128,10,4} is fused");
-    return LNRF_ERR_UNSUPPORTED;
-  }
+  LNRF_REQUIRE_NERF_SHAPE(shape);
   LNRF_CHECK_ARG(params && packed, "null pointer");
   hipLaunchKernelGGL(nerf_pack_kernel, dim3(640), dim3(256), 0, as_stream(stream), params, (char*)packed);
   LNRF_LAUNCH_CHECK();
   return LNRF_OK;
 }
 
-template <class K>
-static int ensure_lds(K kernel, int bytes) {
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-  if (e != hipSuccess) return hip_fail(e, "hipFuncSetAttribute(max dynamic LDS)");
-  return LNRF_OK;
-}
-
-static int nerf_fwd_launch(const lnrf_nerf_shape* shape, const void* packed, const float* x, const float* d,
-                           const float* rays, int64_t ray_stride, const float* ts, int32_t t, int64_t m,
-                           float* density, float* rgb, void* save, bool hidden_masks, lnrf_stream_t stream) {
-  if (!shape_supported(shape)) {
-    set_error("lnrf_nerf_mlp_fwd: only the default NeRFModel shape {5,4,256,128,10,4} is fused");
-    return LNRF_ERR_UNSUPPORTED;
-  }
+static int nerf_fwd_launch(const void* packed, const float* x, const float* d, const float* rays, int64_t ray_stride,
+                           const float* ts, int32_t t, int64_t m, float* density, float* rgb, void* save,
+                           bool hidden_masks, lnrf_stream_t stream) {
   LNRF_CHECK_ARG(packed && density && rgb, "null pointer");
   LNRF_CHECK_ARG(m >= 0, "bad m");
   const bool from_rays = rays != nullptr;
   if (from_rays) LNRF_CHECK_ARG(ts && t >= 1 && ray_stride >= 6 && m % t == 0, "rays mode needs ts, t, m = n*t");
   else LNRF_CHECK_ARG(x && d, "need x and d (or rays and ts)");
   if (m == 0) return LNRF_OK;
-  const int64_t n_tiles = tiles_for(m);
+  const int64_t n_tiles = padded_tiles(m);
   const dim3 grid((unsigned)((n_tiles + kWaves - 1) / kWaves)), block(kThreads);
   hipStream_t st = as_stream(stream);
   int rc;
 #define LAUNCH_FWD(SAVE, RAYS, HM)                                                                        \
   do {                                                                                                    \
-    rc = ensure_lds(nerf_fwd_kernel<SAVE, RAYS, HM>, kFusedLds);                                          \
+    rc = set_max_dynamic_lds(nerf_fwd_kernel<SAVE, RAYS, HM>, kFusedLds);                                 \
     if (rc) return rc;                                                                                    \
     hipLaunchKernelGGL((nerf_fwd_kernel<SAVE, RAYS, HM>), grid, block, kFusedLds, st, (const char*)packed, \
                        x, d, rays, ray_stride, ts, (int)t, m, n_tiles, density, rgb, (char*)save);        \
@@ -620,26 +590,25 @@ extern "C" int lnrf_nerf_mlp_fwd(const lnrf_nerf_shape* shape, const void* packe
                                  const float* d, const float* rays, int64_t ray_stride, const float* ts,
                                  int32_t t, int64_t m, float* density, float* rgb, void* save,
                                  lnrf_stream_t stream) {
-  return nerf_fwd_launch(shape, packed, x, d, rays, ray_stride, ts, t, m, density, rgb, save, true, stream);
+  LNRF_REQUIRE_NERF_SHAPE(shape);
+  return nerf_fwd_launch(packed, x, d, rays, ray_stride, ts, t, m, density, rgb, save, true, stream);
 }
 
 extern "C" int lnrf_nerf_mlp_fwd_ls(const lnrf_nerf_shape* shape, const void* packed, const float* x,
                                     const float* d, const float* rays, int64_t ray_stride, const float* ts,
                                     int32_t t, int64_t m, float* density, float* rgb, void* save,
                                     lnrf_stream_t stream) {
-  return nerf_fwd_launch(shape, packed, x, d, rays, ray_stride, ts, t, m, density, rgb, save, false, stream);
+  LNRF_REQUIRE_NERF_SHAPE(shape);
+  return nerf_fwd_launch(packed, x, d, rays, ray_stride, ts, t, m, density, rgb, save, false, stream);
 }
 
 extern "C" int64_t lnrf_nerf_packed_split_bytes(const lnrf_nerf_shape* s) {
-  return shape_supported(s) ? kPack3Bytes : -1;
+  return nerf_shape_fused(s) ? kPack3Bytes : -1;
 }
 
 extern "C" int lnrf_nerf_pack_weights_split(const lnrf_nerf_shape* shape, const float* params, void* packed,
                                             lnrf_stream_t stream) {
-  if (!shape_supported(shape)) {
-    set_error("lnrf_nerf_pack_weights_split: only the default NeRFModel shape {5,4,256,128,10,4} is fused");
-    return LNRF_ERR_UNSUPPORTED;
-  }
+  LNRF_REQUIRE_NERF_SHAPE(shape);
   LNRF_CHECK_ARG(params && packed, "null pointer");
   hipLaunchKernelGGL(nerf_pack_split_kernel, dim3(1024), dim3(256), 0, as_stream(stream), params, (char*)packed);
   LNRF_LAUNCH_CHECK();
@@ -649,10 +618,7 @@ extern "C" int lnrf_nerf_pack_weights_split(const lnrf_nerf_shape* shape, const 
 extern "C" int lnrf_nerf_mlp_fwd_split(const lnrf_nerf_shape* shape, const void* packed_split, const float* x,
                                        const float* d, const float* rays, int64_t ray_stride, const float* ts,
                                        int32_t t, int64_t m, float* density, float* rgb, lnrf_stream_t stream) {
-  if (!shape_supported(shape)) {
-    set_error("lnrf_nerf_mlp_fwd_split: only the default NeRFModel shape {5,4,256,128,10,4} is fused");
-    return LNRF_ERR_UNSUPPORTED;
-  }
+  LNRF_REQUIRE_NERF_SHAPE(shape);
   LNRF_CHECK_ARG(packed_split && density && rgb, "null pointer");
   LNRF_CHECK_ARG(m >= 0, "bad m");
   const bool from_rays = rays != nullptr;
@@ -664,12 +630,12 @@ extern "C" int lnrf_nerf_mlp_fwd_split(const lnrf_nerf_shape* shape, const void*
   hipStream_t st = as_stream(stream);
   int rc;
   if (from_rays) {
-    rc = ensure_lds(nerf_fwd_split_kernel<true>, kFusedLds);
+    rc = set_max_dynamic_lds(nerf_fwd_split_kernel<true>, kFusedLds);
     if (rc) return rc;
     hipLaunchKernelGGL((nerf_fwd_split_kernel<true>), grid, block, kFusedLds, st, (const char*)packed_split, x, d,
                        rays, ray_stride, ts, (int)t, m, density, rgb);
   } else {
-    rc = ensure_lds(nerf_fwd_split_kernel<false>, kFusedLds);
+    rc = set_max_dynamic_lds(nerf_fwd_split_kernel<false>, kFusedLds);
     if (rc) return rc;
     hipLaunchKernelGGL((nerf_fwd_split_kernel<false>), grid, block, kFusedLds, st, (const char*)packed_split, x, d,
                        rays, ray_stride, ts, (int)t, m, density, rgb);
@@ -681,16 +647,13 @@ extern "C" int lnrf_nerf_mlp_fwd_split(const lnrf_nerf_shape* shape, const void*
 extern "C" int lnrf_nerf_mlp_bwd_chain(const lnrf_nerf_shape* shape, const void* packed, const void* save,
                                        const float* density, const float* rgb, const float* g_density,
                                        const float* g_rgb, int64_t m, void* scratch, lnrf_stream_t stream) {
-  if (!shape_supported(shape)) {
-    set_error("lnrf_nerf_mlp_bwd_chain: only the default NeRFModel shape {5,4,256,128,10,4} is fused");
-    return LNRF_ERR_UNSUPPORTED;
-  }
+  LNRF_REQUIRE_NERF_SHAPE(shape);
   LNRF_CHECK_ARG(packed && save && density && rgb && g_density && g_rgb && scratch, "null pointer");
   LNRF_CHECK_ARG(m >= 0, "bad m");
   if (m == 0) return LNRF_OK;
-  const int64_t n_tiles = tiles_for(m);
+  const int64_t n_tiles = padded_tiles(m);
   hipStream_t st = as_stream(stream);
-  int rc = ensure_lds(nerf_bwd_chain_kernel, kFusedLds);
+  int rc = set_max_dynamic_lds(nerf_bwd_chain_kernel, kFusedLds);
   if (rc) return rc;
   hipLaunchKernelGGL(nerf_bwd_chain_kernel, dim3((unsigned)((n_tiles + kWaves - 1) / kWaves)), dim3(kThreads),
                      kFusedLds, st, (const char*)packed, (const char*)save, density, rgb, g_density, g_rgb, m,
@@ -699,24 +662,23 @@ extern "C" int lnrf_nerf_mlp_bwd_chain(const lnrf_nerf_shape* shape, const void*
   return LNRF_OK;
 }
 
-int lnrf::launch_nerf_wgrad(const WgradArgs& args, int blocks, const void* xbuf, const void* ybuf, int64_t n_tiles,
-                            float* grads, hipStream_t stream, WgLayout lay, float* slabs, bool plain, bool fold) {
-  LNRF_CHECK_ARG(slabs != nullptr && blocks <= kNerfWgradBlocks, "needs slabs for at most 512 workgroups");
+int lnrf::launch_nerf_wgrad(const WgradList& list, const void* xbuf, const void* ybuf, int64_t n_tiles, float* grads,
+                            hipStream_t stream, WgLayout lay, float* slabs, bool plain, bool fold) {
+  LNRF_CHECK_ARG(slabs != nullptr && list.blocks <= kWgradMaxBlocks, "needs slabs, and holds at most kWgradMaxBlocks of them");
   const int lds = 2 * 2 * 36 * kFragBytes;  // largest body: 2 buffers x 2 steps x (4 + 32) fragments
-  hipError_t e = hipFuncSetAttribute(plain ? reinterpret_cast<const void*>(nerf_wgrad_kernel<true>)
-                                           : reinterpret_cast<const void*>(nerf_wgrad_kernel<false>),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-  if (e != hipSuccess) return hip_fail(e, "hipFuncSetAttribute(max dynamic LDS)");
+  const dim3 grid((unsigned)list.blocks), block(kThreads);
+  int rc = plain ? set_max_dynamic_lds(nerf_wgrad_kernel<true>, lds) : set_max_dynamic_lds(nerf_wgrad_kernel<false>, lds);
+  if (rc) return rc;
   if (plain)
-    hipLaunchKernelGGL(nerf_wgrad_kernel<true>, dim3((unsigned)blocks), dim3(kThreads), lds, stream, args,
-                       (const char*)xbuf, (const char*)ybuf, n_tiles, lay, slabs);
+    hipLaunchKernelGGL(nerf_wgrad_kernel<true>, grid, block, lds, stream, list.args, (const char*)xbuf,
+                       (const char*)ybuf, n_tiles, lay, slabs);
   else
-    hipLaunchKernelGGL(nerf_wgrad_kernel<false>, dim3((unsigned)blocks), dim3(kThreads), lds, stream, args,
-                       (const char*)xbuf, (const char*)ybuf, n_tiles, lay, slabs);
+    hipLaunchKernelGGL(nerf_wgrad_kernel<false>, grid, block, lds, stream, list.args, (const char*)xbuf,
+                       (const char*)ybuf, n_tiles, lay, slabs);
   LNRF_LAUNCH_CHECK();
   if (fold) {
-    hipLaunchKernelGGL(nerf_wgrad_reduce_kernel, dim3((unsigned)(args.n_problems * kWaves * kSlabMaxTiles)), dim3(64 * kSlabReduceWaves), 0, stream, args,
-                       (const float*)slabs, grads);
+    hipLaunchKernelGGL(nerf_wgrad_reduce_kernel, dim3((unsigned)(list.args.n_problems * kWaves * kSlabMaxTiles)),
+                       dim3(64 * kSlabReduceWaves), 0, stream, list.args, (const float*)slabs, grads);
     LNRF_LAUNCH_CHECK();
   }
   return LNRF_OK;
@@ -724,26 +686,18 @@ int lnrf::launch_nerf_wgrad(const WgradArgs& args, int blocks, const void* xbuf,
 
 extern "C" int lnrf_nerf_mlp_bwd_weights(const lnrf_nerf_shape* shape, const void* save, void* scratch,
                                          int64_t m, float* grads, lnrf_stream_t stream) {
-  if (!shape_supported(shape)) {
-    set_error("lnrf_nerf_mlp_bwd_weights: only the default NeRFModel shape {5,4,256,128,10,4} is fused");
-    return LNRF_ERR_UNSUPPORTED;
-  }
+  LNRF_REQUIRE_NERF_SHAPE(shape);
   LNRF_CHECK_ARG(save && scratch && grads, "null pointer");
   LNRF_CHECK_ARG(m >= 0, "bad m");
   if (m == 0) return LNRF_OK;
-  const int64_t n_tiles = tiles_for(m);
-  hipStream_t st = as_stream(stream);
-  // weight-gradient problems: ONE launch, heaviest problems first, blocks proportional to bytes (512 in all)
-  WgradArgs a;
-  const int blocks[13] = {48, 48, 48, 48, 47, 47, 47, 47, 39, 30, 30, 18, 15};
-  const int first = build_wgrad_problems(a, blocks, (n_tiles + 5) / 6);
+  const int64_t n_tiles = padded_tiles(m);
   float* slabs = reinterpret_cast<float*>(reinterpret_cast<char*>(scratch) + grad_dump_bytes(m));
   // operand loads (fused_chain.h WgStage::load): ordinary for the big (fine-pass) launch, non-temporal for the small one —
   // measured on this model only (the Ref-NeRF launches are faster with non-temporal loads at every size); in tiles of
   // 32 evaluations
   constexpr int64_t kPlainFrom = 16384;
-  return launch_nerf_wgrad(a, first, save, scratch, n_tiles, grads, st, WgLayout{kSaveTileSlots, kGradTileSlots}, slabs,
-                           n_tiles >= kPlainFrom);
+  return launch_nerf_wgrad(wgrad_list_split(n_tiles), save, scratch, n_tiles, grads, as_stream(stream),
+                           WgLayout{kSaveTileSlots, kGradTileSlots}, slabs, n_tiles >= kPlainFrom);
 }
 
 #ifdef LNRF_TIMELINE

@@ -802,7 +802,6 @@ static bool ngp_supported(const lnrf_ngp_mlp_desc* d) {
          d->color_layers == 2 && d->d_freqs == 4 && d->enc_dim >= 1 && d->enc_dim <= 32;
 }
 // padded to whole workgroups (8 waves): the kernels walk groups of 8 tiles
-static inline int64_t ngp_tiles(int64_t m) { return ((m + kTileCols - 1) / kTileCols + kWaves - 1) / kWaves * kWaves; }
 static NgpOffsets ngp_offsets(const lnrf_ngp_mlp_desc* d) {
   NgpOffsets o;
   int64_t off = d->dense_offset;
@@ -821,14 +820,6 @@ static NgpOffsets ngp_offsets(const lnrf_ngp_mlp_desc* d) {
                  "d_freqs 4, L*F <= 32} is fused");                                                        \
     return LNRF_ERR_UNSUPPORTED;                                                                           \
   }
-
-template <class K>
-static int ngp_ensure_lds(K kernel, int bytes) {
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-  if (e != hipSuccess) return hip_fail(e, "hipFuncSetAttribute(max dynamic LDS)");
-  return LNRF_OK;
-}
 
 extern "C" int64_t lnrf_ngp_mlp_packed_bytes(const lnrf_ngp_mlp_desc* desc) {
   return ngp_supported(desc) ? kNgpPackBytes : -1;
@@ -851,7 +842,7 @@ static int64_t ngp_lmax_off(const lnrf_ngp_mlp_desc* d, int64_t n_tiles) {
 }
 
 extern "C" int64_t lnrf_ngp_mlp_scratch_bytes(const lnrf_ngp_mlp_desc* desc, int64_t m) {
-  return ngp_supported(desc) ? ngp_lmax_off(desc, ngp_tiles(m)) + ngp_lmax_bytes(ngp_tiles(m)) : -1;
+  return ngp_supported(desc) ? ngp_lmax_off(desc, padded_tiles(m)) + ngp_lmax_bytes(padded_tiles(m)) : -1;
 }
 
 extern "C" int lnrf_ngp_mlp_pack(const lnrf_ngp_mlp_desc* desc, const float* params, void* packed,
@@ -888,7 +879,7 @@ extern "C" int lnrf_ngp_mlp_fwd_split(const lnrf_ngp_mlp_desc* desc, const void*
   LNRF_CHECK_ARG(m >= 0, "bad m");
   if (m == 0) return LNRF_OK;
   LNRF_CHECK_ARG(packed_split && enc_t && d && density && rgb, "null pointer");
-  const int64_t n_tiles = ngp_tiles(m);
+  const int64_t n_tiles = padded_tiles(m);
   int dev = 0, cus = 0;
   hipError_t e = hipGetDevice(&dev);
   if (e == hipSuccess) e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
@@ -898,12 +889,12 @@ extern "C" int lnrf_ngp_mlp_fwd_split(const lnrf_ngp_mlp_desc* desc, const void*
   hipStream_t st = as_stream(stream);
   int rc;
   if (desc->enc_dim <= 16) {
-    rc = ngp_ensure_lds(ngp_mlp_fwd_split_kernel<1>, kNgpSplitBytes);
+    rc = set_max_dynamic_lds(ngp_mlp_fwd_split_kernel<1>, kNgpSplitBytes);
     if (rc) return rc;
     hipLaunchKernelGGL((ngp_mlp_fwd_split_kernel<1>), dim3((unsigned)nb), dim3(kThreads), kNgpSplitBytes, st,
                        (const char*)packed_split, enc_t, d, (int)desc->enc_dim, m, n_tiles, density, rgb);
   } else {
-    rc = ngp_ensure_lds(ngp_mlp_fwd_split_kernel<2>, kNgpSplitBytes);
+    rc = set_max_dynamic_lds(ngp_mlp_fwd_split_kernel<2>, kNgpSplitBytes);
     if (rc) return rc;
     hipLaunchKernelGGL((ngp_mlp_fwd_split_kernel<2>), dim3((unsigned)nb), dim3(kThreads), kNgpSplitBytes, st,
                        (const char*)packed_split, enc_t, d, (int)desc->enc_dim, m, n_tiles, density, rgb);
@@ -918,17 +909,17 @@ extern "C" int lnrf_ngp_mlp_fwd(const lnrf_ngp_mlp_desc* desc, const void* packe
   LNRF_CHECK_ARG(m >= 0, "bad m");
   if (m == 0) return LNRF_OK;
   LNRF_CHECK_ARG(packed && enc_t && d && density && rgb, "null pointer");
-  const int64_t n_tiles = ngp_tiles(m);
+  const int64_t n_tiles = padded_tiles(m);
   const dim3 grid((unsigned)((n_tiles + kWaves - 1) / kWaves)), block(kThreads);
   hipStream_t st = as_stream(stream);
   int rc;
   if (desc->enc_dim <= 16) {
-    rc = ngp_ensure_lds(ngp_mlp_kernel<1, false>, kNgpLds);
+    rc = set_max_dynamic_lds(ngp_mlp_kernel<1, false>, kNgpLds);
     if (rc) return rc;
     hipLaunchKernelGGL((ngp_mlp_kernel<1, false>), grid, block, kNgpLds, st, (const char*)packed, enc_t, d,
                        (int)desc->enc_dim, m, n_tiles, density, rgb, nullptr, nullptr, nullptr, nullptr);
   } else {
-    rc = ngp_ensure_lds(ngp_mlp_kernel<2, false>, kNgpLds);
+    rc = set_max_dynamic_lds(ngp_mlp_kernel<2, false>, kNgpLds);
     if (rc) return rc;
     hipLaunchKernelGGL((ngp_mlp_kernel<2, false>), grid, block, kNgpLds, st, (const char*)packed, enc_t, d,
                        (int)desc->enc_dim, m, n_tiles, density, rgb, nullptr, nullptr, nullptr, nullptr);
@@ -945,7 +936,7 @@ extern "C" int lnrf_ngp_mlp_bwd(const lnrf_ngp_mlp_desc* desc, const void* packe
   LNRF_CHECK_ARG(m >= 0, "bad m");
   if (m == 0) return LNRF_OK;
   LNRF_CHECK_ARG(packed && enc_t && d && g_density && g_rgb && scratch && g_enc_t && grads, "null pointer");
-  const int64_t n_tiles = ngp_tiles(m);
+  const int64_t n_tiles = padded_tiles(m);
   hipStream_t st = as_stream(stream);
   int rc;
   // per-workgroup rows of level maxima live behind the partial dW rows in the scratch buffer
@@ -992,13 +983,13 @@ extern "C" int lnrf_ngp_mlp_bwd(const lnrf_ngp_mlp_desc* desc, const void* packe
   const int pstride = ngp_pstride(desc);
   float* wparts = reinterpret_cast<float*>(scratch);
   if (desc->enc_dim <= 16) {
-    rc = ngp_ensure_lds(ngp_mlp_kernel<1, true>, kNgpFusedLds);
+    rc = set_max_dynamic_lds(ngp_mlp_kernel<1, true>, kNgpFusedLds);
     if (rc) return rc;
     hipLaunchKernelGGL((ngp_mlp_kernel<1, true>), pgrid, block, kNgpFusedLds, st, (const char*)packed, enc_t, d,
                        (int)desc->enc_dim, m, n_tiles, nullptr, nullptr, g_density, g_rgb, nullptr, g_enc_t,
                        lmax_parts, a, wparts, pstride, (int64_t)desc->dense_offset);
   } else {
-    rc = ngp_ensure_lds(ngp_mlp_kernel<2, true>, kNgpFusedLds);
+    rc = set_max_dynamic_lds(ngp_mlp_kernel<2, true>, kNgpFusedLds);
     if (rc) return rc;
     hipLaunchKernelGGL((ngp_mlp_kernel<2, true>), pgrid, block, kNgpFusedLds, st, (const char*)packed, enc_t, d,
                        (int)desc->enc_dim, m, n_tiles, nullptr, nullptr, g_density, g_rgb, nullptr, g_enc_t,

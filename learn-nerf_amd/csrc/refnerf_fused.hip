@@ -273,57 +273,6 @@ __global__ __launch_bounds__(kThreads) void refnerf_normal_kernel(
   }
 }
 
-// ---------------------------------------------------------------------------------------------
-// trunk backward, chain part: d L / d spatial_out [M, ldg] (fp32) -> dy_8 .. dy_0 dumps
-// ---------------------------------------------------------------------------------------------
-constexpr int kHiddenBwdOff = bwd_base(2);                 // fragments of T0 / T1 (unused by this model)
-constexpr int kHiddenBwdFrags = kBwdFrags - kHiddenBwdOff;  // 8 x 128
-static_assert(kHiddenBwdOff % kStageFrags == 0 && kHiddenBwdFrags == 1024, "hidden part of the transposed stream");
-
-__global__ __launch_bounds__(kThreads) void refnerf_trunk_bwd_chain_kernel(
-    const char* __restrict__ packed, const char* __restrict__ save, const float* __restrict__ g_z, int64_t ldg,
-    int64_t M, int64_t n_tiles, char* __restrict__ gdump) {
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int c = lane & 31, h = lane >> 5;
-  const int64_t tile = (int64_t)blockIdx.x * kWaves + wave;
-  const int64_t m = tile * kTileCols + c;
-  const bool valid = m < M;
-  uint4 mask[8];
-  load_relu_masks(mask, save, n_tiles, tile, lane);
-  bf16x8 a0[16], a1[16];
-  // seed dy_8 = bf16(d L / d spatial_out): k slot (ks, h, j) <-> feature 16 ks + 8 (j >> 2) + 4 h + (j & 3)
-  static_for<16>([&](auto ks_) {
-    constexpr int ks = decltype(ks_)::value;
-    float4 lo = make_float4(0, 0, 0, 0), hi = make_float4(0, 0, 0, 0);
-    if (valid) {
-      const float* gr = g_z + m * ldg + 16 * ks + 4 * h;
-      lo = *reinterpret_cast<const float4*>(gr);
-      hi = *reinterpret_cast<const float4*>(gr + 8);
-    }
-    a1[ks][0] = (__bf16)lo.x; a1[ks][1] = (__bf16)lo.y; a1[ks][2] = (__bf16)lo.z; a1[ks][3] = (__bf16)lo.w;
-    a1[ks][4] = (__bf16)hi.x; a1[ks][5] = (__bf16)hi.y; a1[ks][6] = (__bf16)hi.z; a1[ks][7] = (__bf16)hi.w;
-  });
-  __syncthreads();
-  Ring<kHiddenBwdFrags / kStageFrags, LinSeq<kHiddenBwdFrags>> ring;
-  ring.stream = packed + kPackBwdOff + (int64_t)kHiddenBwdOff * kFragBytes;
-  ring.wave = wave;
-  ring.lane = lane;
-  ring.prologue();
-  DumpAddr gd{gdump, n_tiles, tile, c, h, kGradTileSlots};
-#pragma unroll
-  for (int i = 0; i < 16; ++i) stream_store(gd.at(grad_dy_slot(8) + i), frag_to_bits(a1[i]));
-  hidden_back<0 * 128, 8>(ring, a1, a0, mask[7], gd);
-  hidden_back<1 * 128, 7>(ring, a0, a1, mask[6], gd);
-  hidden_back<2 * 128, 6>(ring, a1, a0, mask[5], gd);
-  hidden_back<3 * 128, 5>(ring, a0, a1, mask[4], gd);
-  hidden_back<4 * 128, 4>(ring, a1, a0, mask[3], gd);
-  hidden_back<5 * 128, 3>(ring, a0, a1, mask[2], gd);
-  hidden_back<6 * 128, 2>(ring, a1, a0, mask[1], gd);
-  hidden_back<7 * 128, 1>(ring, a0, a1, mask[0], gd);
-}
-
 // seed of the layer-stationary trunk backward: dy_8 = bf16(d L / d spatial_out) as the 16 fragments of the dump's dy8 slots
 __global__ __launch_bounds__(kThreads) void refnerf_dy8_kernel(const float* __restrict__ g_z, int64_t ldg, int64_t M,
                                                                int64_t n_tiles, char* __restrict__ gdump) {
@@ -953,13 +902,6 @@ __global__ void refnerf_pack_kernel(const float* __restrict__ params, char* __re
 
 using namespace lnrf;
 
-template <class K>
-static int set_lds(K kernel, int bytes) {
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                     bytes);
-  if (e != hipSuccess) return hip_fail(e, "hipFuncSetAttribute(max dynamic LDS)");
-  return LNRF_OK;
-}
 static inline dim3 tile_grid(int64_t n_tiles) { return dim3((unsigned)(n_tiles / kWaves)); }
 
 extern "C" int64_t lnrf_refnerf_render_packed_bytes(void) { return kRef3Bytes; }
@@ -983,7 +925,7 @@ extern "C" int lnrf_refnerf_trunk_normal_split(const void* packed_split, const f
   LNRF_CHECK_ARG(m >= 0 && ld >= 256 && ld % 4 == 0 && ((uintptr_t)spatial_out & 15) == 0,
                  "spatial_out rows must be 16-byte aligned (ld a multiple of 4, >= 256)");
   if (m == 0) return LNRF_OK;
-  int rc = set_lds(refnerf_render_split_kernel, kRefLds);
+  int rc = set_max_dynamic_lds(refnerf_render_split_kernel, kRefLds);
   if (rc) return rc;
   const int64_t tiles = (m + kTileCols - 1) / kTileCols;
   hipLaunchKernelGGL(refnerf_render_split_kernel, dim3((unsigned)((tiles + kSplitWaves - 1) / kSplitWaves)),
@@ -998,7 +940,7 @@ extern "C" int lnrf_refnerf_dir_fwd_split(const void* packed_split, const float*
   LNRF_CHECK_ARG(packed_split && dir_in && dir_out, "null pointer");
   LNRF_CHECK_ARG(m >= 0 && ld >= 273 && ld % 4 == 0 && ((uintptr_t)dir_in & 15) == 0, "dir_in rows must be 16-byte aligned");
   if (m == 0) return LNRF_OK;
-  int rc = set_lds(refnerf_dir_fwd_split_kernel, kDirLds);
+  int rc = set_max_dynamic_lds(refnerf_dir_fwd_split_kernel, kDirLds);
   if (rc) return rc;
   const int64_t tiles = (m + kTileCols - 1) / kTileCols;
   hipLaunchKernelGGL(refnerf_dir_fwd_split_kernel, dim3((unsigned)((tiles + kSplitWaves - 1) / kSplitWaves)),
@@ -1022,8 +964,8 @@ extern "C" int lnrf_refnerf_trunk_fwd(const void* packed, const float* x, int64_
   LNRF_CHECK_ARG(m >= 0 && ld >= 256 && ld % 4 == 0 && ((uintptr_t)spatial_out & 15) == 0,
                  "spatial_out rows must be 16-byte aligned (ld a multiple of 4, >= 256)");
   if (m == 0) return LNRF_OK;
-  const int64_t n_tiles = nerf_tiles_for(m);
-  int rc = set_lds(refnerf_trunk_fwd_kernel, kRefLds);
+  const int64_t n_tiles = padded_tiles(m);
+  int rc = set_max_dynamic_lds(refnerf_trunk_fwd_kernel, kRefLds);
   if (rc) return rc;
   hipLaunchKernelGGL(refnerf_trunk_fwd_kernel, tile_grid(n_tiles), dim3(kThreads), kRefLds, as_stream(stream),
                      (const char*)packed, x, m, n_tiles, (char*)save, spatial_out, ld);
@@ -1036,8 +978,8 @@ extern "C" int lnrf_refnerf_normal_pass(const void* packed, const void* save, co
   LNRF_CHECK_ARG(packed && save && x && cdump && nraw, "null pointer");
   LNRF_CHECK_ARG(m >= 0, "bad m");
   if (m == 0) return LNRF_OK;
-  const int64_t n_tiles = nerf_tiles_for(m);
-  int rc = set_lds(refnerf_normal_kernel, kRefLds);
+  const int64_t n_tiles = padded_tiles(m);
+  int rc = set_max_dynamic_lds(refnerf_normal_kernel, kRefLds);
   if (rc) return rc;
   hipLaunchKernelGGL(refnerf_normal_kernel, tile_grid(n_tiles), dim3(kThreads), kRefLds, as_stream(stream),
                      (const char*)packed, (const char*)save, x, m, n_tiles, (char*)cdump, nraw);
@@ -1045,32 +987,6 @@ extern "C" int lnrf_refnerf_normal_pass(const void* packed, const void* save, co
   return LNRF_OK;
 }
 
-// the nine weight-gradient problems of the trunk: Dense_1..8 (hidden x hidden) and x_emb x [dy0 | dy5] (Dense_0 and the
-// x_emb rows of Dense_5: the two dumps are neighbours, nerf_layout.h); 256 workgroups = one per CU (two rounds of 512 cost
-// twice the partial-sum traffic for the same streaming rate)
-// `slabs`: room for 512 workgroups' partial sums (kSlabBlockBytes each) — the slab epilogue of fused_chain.h
-static int trunk_wgrad(const void* xbuf, const void* ybuf, int64_t n_tiles, int do_bias, float* grads, hipStream_t st,
-                       float* slabs) {
-  WgradArgs a;
-  a.n_problems = 0;
-  int first = 0;
-  auto add = [&](int shape, int xs, int ys, int dense, int row_map, int row_off, int bias, int blocks, int col_map) {
-    WgradProblem p;
-    p.shape = shape; p.x_slot0 = xs; p.y_slot0 = ys; p.dense = dense; p.row_map = row_map; p.row_off = row_off;
-    p.col_map = col_map; p.do_bias = bias;
-    p.w_off = p.b_off = p.out_dim = p.n_rows = 0;
-    int64_t nb = blocks;
-    const int64_t cap = (n_tiles + 5) / 6;
-    if (nb > cap) nb = cap;
-    p.first_block = first;
-    p.n_blocks = (int)nb;
-    first += (int)nb;
-    a.p[a.n_problems++] = p;
-  };
-  for (int l = 1; l <= 8; ++l) add(0, kSaveH + (l - 1) * 16, grad_dy_slot(l), l, ROW_HIDDEN, 0, do_bias, 28, COL_256);
-  add(7, kSaveXin, grad_dy_slot(0), 0, ROW_XEMB, 0, do_bias, 32, COL_DY0_DY5);
-  return launch_nerf_wgrad(a, first, xbuf, ybuf, n_tiles, grads, st, WgLayout{kSaveTileSlots, kGradTileSlots}, slabs);
-}
 // the slab region behind a gradient dump that was sized by lnrf_nerf_bwd_scratch_bytes
 static float* slabs_behind_dump(const void* dump, int64_t n_tiles) {
   return reinterpret_cast<float*>(const_cast<char*>(reinterpret_cast<const char*>(dump)) + (int64_t)kGradSlots * n_tiles * kFragBytes);
@@ -1082,7 +998,7 @@ extern "C" int lnrf_refnerf_trunk_bwd(const void* packed, const void* save, cons
   LNRF_CHECK_ARG(m >= 0 && ld >= 256 && ld % 4 == 0 && ((uintptr_t)g_spatial & 15) == 0,
                  "gradient rows must be 16-byte aligned (ld a multiple of 4, >= 256)");
   if (m == 0) return LNRF_OK;
-  const int64_t n_tiles = nerf_tiles_for(m);
+  const int64_t n_tiles = padded_tiles(m);
   // layer-stationary form (nerf_bwd_ls.hip): seed dy8, the pipeline forms dy7..dy0, dW_1..8 and db_1..8; the two x_emb
   // problems (Dense_0, rows 256.. of Dense_5) stay on the split-K kernel.  scratch: lnrf_refnerf_trunk_bwd_scratch_bytes.
   hipLaunchKernelGGL(refnerf_dy8_kernel, tile_grid(n_tiles), dim3(kThreads), 0, as_stream(stream), g_spatial, ld, m, n_tiles,
@@ -1090,25 +1006,8 @@ extern "C" int lnrf_refnerf_trunk_bwd(const void* packed, const void* save, cons
   LNRF_LAUNCH_CHECK();
   int rc = launch_ls_pipeline(packed, save, scratch, m, grads, as_stream(stream));
   if (rc) return rc;
-  WgradArgs a;
-  a.n_problems = 0;
-  int first = 0;
-  {  // x_emb x [dy0 | dy5]: Dense_0 (with its bias) and rows 256.. of Dense_5
-    WgradProblem p;
-    p.shape = 7; p.x_slot0 = kSaveXin; p.y_slot0 = grad_dy_slot(0); p.dense = 0;
-    p.row_map = ROW_XEMB; p.row_off = 0; p.col_map = COL_DY0_DY5; p.do_bias = 1;
-    p.w_off = p.b_off = p.out_dim = p.n_rows = 0;
-    int64_t nb = 256;
-    const int64_t cap = (n_tiles + 5) / 6;
-    if (nb > cap) nb = cap;
-    p.first_block = first;
-    p.n_blocks = (int)nb;
-    first += (int)nb;
-    a.p[a.n_problems++] = p;
-  }
-  float* small_slabs = reinterpret_cast<float*>(reinterpret_cast<char*>(scratch) + ls_small_slab_off(m));
-  return launch_nerf_wgrad(a, first, save, scratch, n_tiles, grads, as_stream(stream),
-                           WgLayout{kSaveTileSlots, kGradTileSlots}, small_slabs);
+  return launch_nerf_wgrad(wgrad_list_ref_trunk(n_tiles), save, scratch, n_tiles, grads, as_stream(stream),
+                           WgLayout{kSaveTileSlots, kGradTileSlots}, ls_small_slabs(scratch, m));
 }
 
 extern "C" int64_t lnrf_refnerf_trunk_bwd_scratch_bytes(int64_t m) { return m < 0 ? -1 : ls_scratch_bytes(m); }
@@ -1118,19 +1017,20 @@ extern "C" int lnrf_refnerf_normal_bwd(const void* packed, const void* save, con
   LNRF_CHECK_ARG(packed && save && cdump && x && u && scratch && grads, "null pointer");
   LNRF_CHECK_ARG(m >= 0, "bad m");
   if (m == 0) return LNRF_OK;
-  const int64_t n_tiles = nerf_tiles_for(m);
-  int rc = set_lds(refnerf_tangent_kernel, kRefLds);
+  const int64_t n_tiles = padded_tiles(m);
+  int rc = set_max_dynamic_lds(refnerf_tangent_kernel, kRefLds);
   if (rc) return rc;
   hipLaunchKernelGGL(refnerf_tangent_kernel, tile_grid(n_tiles), dim3(kThreads), kRefLds, as_stream(stream),
                      (const char*)packed, (const char*)save, x, u, m, n_tiles, (char*)scratch);
   LNRF_LAUNCH_CHECK();
   // the partial sums go behind the chain-state dump (cdump is sized by lnrf_nerf_bwd_scratch_bytes: dump + slab region)
-  return trunk_wgrad(scratch, cdump, n_tiles, 0, grads, as_stream(stream), slabs_behind_dump(cdump, n_tiles));
+  return launch_nerf_wgrad(wgrad_list_ref_normal(n_tiles), scratch, cdump, n_tiles, grads, as_stream(stream),
+                           WgLayout{kSaveTileSlots, kGradTileSlots}, slabs_behind_dump(cdump, n_tiles));
 }
 
-extern "C" int64_t lnrf_refnerf_dir_save_bytes(int64_t m) { return (int64_t)kDirSaveSlots * nerf_tiles_for(m) * kFragBytes; }
+extern "C" int64_t lnrf_refnerf_dir_save_bytes(int64_t m) { return (int64_t)kDirSaveSlots * padded_tiles(m) * kFragBytes; }
 extern "C" int64_t lnrf_refnerf_dir_scratch_bytes(int64_t m) {  // gradient dump, then the slab region of the weight-gradient launch
-  return (int64_t)kDirGradSlots * nerf_tiles_for(m) * kFragBytes + 512 * kSlabBlockBytes;
+  return (int64_t)kDirGradSlots * padded_tiles(m) * kFragBytes + kWgradSlabBytes;
 }
 
 extern "C" int lnrf_refnerf_dir_fwd(const void* packed, const float* dir_in, int64_t ld, int64_t m, void* dsave,
@@ -1139,8 +1039,8 @@ extern "C" int lnrf_refnerf_dir_fwd(const void* packed, const float* dir_in, int
   LNRF_CHECK_ARG(m >= 0 && ld >= 276 && ld % 4 == 0 && ((uintptr_t)dir_in & 15) == 0,
                  "dir_in rows must be 16-byte aligned (ld a multiple of 4, >= 276)");
   if (m == 0) return LNRF_OK;
-  const int64_t n_tiles = nerf_tiles_for(m);
-  int rc = set_lds(refnerf_dir_fwd_kernel, kDirLds);
+  const int64_t n_tiles = padded_tiles(m);
+  int rc = set_max_dynamic_lds(refnerf_dir_fwd_kernel, kDirLds);
   if (rc) return rc;
   hipLaunchKernelGGL(refnerf_dir_fwd_kernel, tile_grid(n_tiles), dim3(kThreads), kDirLds, as_stream(stream),
                      (const char*)packed, dir_in, ld, m, n_tiles, (char*)dsave, dir_out);
@@ -1154,32 +1054,13 @@ extern "C" int lnrf_refnerf_dir_bwd(const void* packed, const void* dsave, const
   LNRF_CHECK_ARG(m >= 0 && ld >= 276 && ld % 4 == 0 && ((uintptr_t)g_dir_in & 15) == 0,
                  "g_dir_in rows must be 16-byte aligned (ld a multiple of 4, >= 276)");
   if (m == 0) return LNRF_OK;
-  const int64_t n_tiles = nerf_tiles_for(m);
-  int rc = set_lds(refnerf_dir_bwd_kernel, kDirLds);
+  const int64_t n_tiles = padded_tiles(m);
+  int rc = set_max_dynamic_lds(refnerf_dir_bwd_kernel, kDirLds);
   if (rc) return rc;
   hipLaunchKernelGGL(refnerf_dir_bwd_kernel, tile_grid(n_tiles), dim3(kThreads), kDirLds, as_stream(stream),
                      (const char*)packed, (const char*)dsave, g_dir_out, m, n_tiles, (char*)scratch, g_dir_in, ld);
   LNRF_LAUNCH_CHECK();
-  // weight gradients: Dense_9 = [input fragments]^T dy9 (273 x 128 + bias), Dense_10 = relu(Dense_9)^T dy10 (128 x 3 + bias)
-  WgradArgs a;
-  a.n_problems = 0;
-  int first = 0;
-  auto add = [&](int shape, int xs, int ys, int out_dim, int n_rows, int w_off, int b_off, int blocks) {
-    WgradProblem p;
-    p.shape = shape; p.x_slot0 = xs; p.y_slot0 = ys; p.dense = 0; p.row_map = ROW_HIDDEN; p.row_off = 0;
-    p.col_map = COL_EXPLICIT; p.do_bias = 1;
-    p.w_off = w_off; p.b_off = b_off; p.out_dim = out_dim; p.n_rows = n_rows;
-    int64_t nb = blocks;
-    const int64_t cap = (n_tiles + 5) / 6;
-    if (nb > cap) nb = cap;
-    p.first_block = first;
-    p.n_blocks = (int)nb;
-    first += (int)nb;
-    a.p[a.n_problems++] = p;
-  };
-  add(5, kDirSaveXin, kDirGradDy9, kDirHidden, kDirIn, kDirW9, kDirB9, 200);  // 256 workgroups = one per CU
-  add(4, kDirSaveH, kDirGradDy10, 3, kDirHidden, kDirW10, kDirB10, 56);
   float* slabs = reinterpret_cast<float*>(reinterpret_cast<char*>(scratch) + (int64_t)kDirGradSlots * n_tiles * kFragBytes);
-  return launch_nerf_wgrad(a, first, dsave, scratch, n_tiles, grads, as_stream(stream),
+  return launch_nerf_wgrad(wgrad_list_ref_dir(n_tiles), dsave, scratch, n_tiles, grads, as_stream(stream),
                            WgLayout{kDirSaveTileSlots, kDirGradTileSlots}, slabs);
 }

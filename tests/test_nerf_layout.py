@@ -226,3 +226,88 @@ def test_slot_orders_keep_the_merged_weight_gradient_operands_adjacent(H):
     assert G(2, 5) == G(2, 0) + 16                                       # dy5 right behind dy0
     assert sorted(dy) == list(range(G(1, 0) + 10, G(3, 0), 16)) and all(v % 2 == 0 for v in dy)
     assert G(0, 0) == 0 and G(1, 0) == 2 and G(3, 0) == 156
+
+
+WGRAD_LISTS = {"split": 0, "ls_finish": 1, "ref_trunk": 2, "ref_normal": 3, "ref_dir": 4}
+
+
+def _expected_owners(which):
+    """0/1 per entry of the gradient vector: what the caller of that list is documented to add to (include/lnrf.h)."""
+    n = 593_924
+    want = np.zeros(n, np.int32)
+    off = 0
+    kernels, biases = [], []
+    for fi, fo in OM.nerf_layer_dims():
+        kernels.append((off, fi, fo))
+        biases.append((off + fi * fo, fo))
+        off += fi * fo + fo
+    assert off == n
+
+    def kernel(l, row0=0, row1=None):
+        o, fi, fo = kernels[l]
+        want[o + row0 * fo:o + (fi if row1 is None else row1) * fo] = 1
+
+    def bias(l):
+        o, fo = biases[l]
+        want[o:o + fo] = 1
+
+    if which == "split":  # everything
+        want[:] = 1
+    elif which == "ls_finish":  # the complement of what the pipeline owns: Dense_1..8 kernel rows 0..255 and biases
+        want[:] = 1
+        for l in range(1, 9):
+            o, fi, fo = kernels[l]
+            want[o:o + 256 * fo] = 0
+            want[biases[l][0]:biases[l][0] + fo] = 0
+    elif which == "ref_trunk":  # behind the same pipeline: Dense_0 and the x_emb rows of Dense_5
+        kernel(0)
+        bias(0)
+        kernel(5, 256)
+    elif which == "ref_normal":  # d L / d Dense_0..8 through n_raw: kernels only
+        for l in range(9):
+            kernel(l)
+    return want
+
+
+@pytest.mark.parametrize("n_tiles", [8, 48, 1 << 16])
+@pytest.mark.parametrize("which", list(WGRAD_LISTS))
+def test_every_gradient_entry_has_exactly_one_owner(H, which, n_tiles):
+    """nerf_wgrad.h: the fold of a weight-gradient launch adds to the gradient vector with a plain read-modify-write, so
+    every entry a caller is responsible for must belong to exactly one (problem, wave, tile, lane, register) and no other
+    entry to any.  Walks the production problem lists and index arithmetic (the code nerf_wgrad_reduce_kernel runs)."""
+    C = H.lnrf_host_wgrad_const
+    capacity, max_tiles, max_to, n_params = C(0), C(1), C(2), C(3)
+    assert n_params == 593_924
+    lid = WGRAD_LISTS[which]
+    info = np.zeros((13, 6), np.int32)
+    H.lnrf_host_wgrad_list.argtypes = [ctypes.c_int, ctypes.c_int64, ctypes.c_void_p]
+    n_prob = H.lnrf_host_wgrad_list(lid, n_tiles, info.ctypes.data)
+    assert n_prob == {"split": 13, "ls_finish": 3, "ref_trunk": 1, "ref_normal": 9, "ref_dir": 2}[which]
+    info = info[:n_prob]
+    # workgroup ranges: contiguous from 0, none empty, within the slab region; shapes within a slab
+    assert (info[:, 1] >= 1).all()
+    assert info[0, 0] == 0 and (info[1:, 0] == info[:-1, 0] + info[:-1, 1]).all()
+    assert info[:, 1].sum() <= capacity
+    assert (info[:, 2] <= max_tiles).all() and (info[:, 3] <= max_to).all()
+    if which == "ls_finish":
+        assert (info[:, 5] == 1).all(), "nerf_ls_fold_kernel must carry every shape of the finish phase"
+    if which == "ref_normal":
+        assert (info[:, 4] == 0).all()
+
+    # RefNERFModel's vector is longer than NeRFModel's behind Dense_8: count over a vector that holds both
+    n = max(n_params, C(7) + 3) + 1024
+    counts = np.zeros(n, np.int32)
+    H.lnrf_host_wgrad_owners.argtypes = [ctypes.c_int, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64]
+    H.lnrf_host_wgrad_owners.restype = ctypes.c_int64
+    assert H.lnrf_host_wgrad_owners(lid, n_tiles, counts.ctypes.data, n) == 0
+    if which == "ref_dir":
+        w9, b9, w10, b10 = C(4), C(5), C(6), C(7)
+        assert (b9, w10, b10) == (w9 + 273 * 128, w9 + 273 * 128 + 128, w9 + 273 * 128 + 128 + 128 * 3)
+        want = np.zeros(n, np.int32)
+        want[w9:b10 + 3] = 1
+    else:
+        want = np.concatenate([_expected_owners(which), np.zeros(n - n_params, np.int32)])
+    assert want.sum() > 0
+    missing, twice, stray = (counts == 0) & (want == 1), counts > 1, (counts > 0) & (want == 0)
+    assert not missing.any() and not twice.any() and not stray.any(), (
+        f"{which}: {missing.sum()} unowned, {twice.sum()} owned more than once, {stray.sum()} outside the caller's entries")
