@@ -59,6 +59,19 @@ __device__ __forceinline__ bf16x8 bits_to_frag(uint4 v) { return __builtin_bit_c
 __device__ __forceinline__ uint4 frag_to_bits(bf16x8 v) { return __builtin_bit_cast(uint4, v); }
 __device__ __forceinline__ bf16x8 zero_frag() { return bits_to_frag(make_uint4(0, 0, 0, 0)); }
 
+// A wave-uniform global address pinned to a scalar register pair.  The empty asm hides the sum from the optimiser:
+// without it the compiler folds a slot's constant offset (slots are 1 KiB apart, the instruction's immediate reaches
+// 4 KiB) back into one 64-bit per-lane address and rebuilds that with a v_add_co / v_addc_co pair per load and store.
+// With it a load or store is (scalar base, 32-bit lane offset, immediate) and the base costs two scalar additions.
+// The caller guarantees uniformity: every kernel here derives the tile from readfirstlane(wave).
+typedef __attribute__((address_space(1))) char gchar;
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ gchar* uniform_global(const void* p) {
+  uint64_t a = reinterpret_cast<uint64_t>(p);
+  asm("" : "+s"(a));
+  return (gchar*)a;
+}
+
 
 // The weight ring.  A stage is 16 fragments (16 KiB) shared by the 8 waves; every wave moves 2 of
 // them.  Staging is global -> VGPR -> LDS (not LDS-DMA: hipcc drains vmcnt(0) before any ds_read
@@ -83,8 +96,9 @@ struct Ring {
 #pragma unroll
     for (int q = 0; q < kPerWave; ++q) {
       const int f = wave + NW * q;
-      r[T & 1][q] = *reinterpret_cast<const uint4*>(stream + ((int64_t)T * kStageFrags + f) * kFragBytes +
-                                                    lane * 16);
+      const gchar* frag = uniform_global(stream + ((int64_t)T * kStageFrags + f) * kFragBytes);
+      const u32x4 v = *reinterpret_cast<const __attribute__((address_space(1))) u32x4*>(frag + (unsigned)(lane * 16));
+      r[T & 1][q] = make_uint4(v[0], v[1], v[2], v[3]);
     }
   }
   template <int T>
@@ -161,17 +175,29 @@ __device__ __forceinline__ f32x16 zero_acc() {
   return acc;
 }
 
-// registers 8s..8s+7 of an accumulator tile -> B-frag of k-step s of the next layer
+// registers 8s..8s+7 of an accumulator tile -> B-frag of k-step s of the next layer.
+// Two registers per v_cvt_pk_bf16_f32, and ReLU afterwards on the packed pair as the signed 16-bit maximum with 0
+// (v_pk_max_i16): rounding never changes a sign and a negative bf16, -0 included, is a negative int16, so this is
+// bf16(max(v, 0)) bit for bit (tests/test_relu_packed_bf16.py) in 8 instead of 20 VALU operations per fragment.  A
+// max in fp32 costs two operations per element here (the compiler canonicalises the operand with a v_max_f32 of
+// its own first).  Only a NaN differs: max(v, 0) in fp32 made it 0, the packed form leaves a positive NaN a NaN.
+typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+typedef short s16x2 __attribute__((ext_vector_type(2)));
 template <int S, bool RELU>
 __device__ __forceinline__ bf16x8 acc_to_frag(const f32x16& acc) {
-  bf16x8 f;
+  u32x4 w;
 #pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    float v = acc[8 * S + j];
-    if (RELU) v = __builtin_amdgcn_fmed3f(v, 0.0f, __builtin_inff());  // max(v, 0) in one VALU op
-    f[j] = (__bf16)v;
+  for (int p = 0; p < 4; ++p) {
+    const f32x2 v = {acc[8 * S + 2 * p], acc[8 * S + 2 * p + 1]};
+    bf16x2 b = __builtin_convertvector(v, bf16x2);
+    if (RELU) {
+      const s16x2 zero = {0, 0};
+      b = __builtin_bit_cast(bf16x2, __builtin_elementwise_max(__builtin_bit_cast(s16x2, b), zero));
+    }
+    w[p] = __builtin_bit_cast(unsigned, b);
   }
-  return f;
+  return __builtin_bit_cast(bf16x8, w);
 }
 
 // ReLU mask of one out-tile from its two bf16 output fragments: bit 8s + j set <=> element j of
@@ -198,10 +224,9 @@ __device__ __forceinline__ bf16x8 masked_frag(const f32x16& acc, unsigned bits, 
 
 // the activation / gradient dumps are written once and read by a later kernel: non-temporal stores keep
 // them from displacing the L2-resident weight stream
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ void stream_store(char* p, uint4 v) {
+__device__ __forceinline__ void stream_store(gchar* p, uint4 v) {
   u32x4 t = {v.x, v.y, v.z, v.w};
-  __builtin_nontemporal_store(t, reinterpret_cast<u32x4*>(p));
+  __builtin_nontemporal_store(t, reinterpret_cast<__attribute__((address_space(1))) u32x4*>(p));
 }
 
 // Byte offset of fragment (slot, tile) in a dump buffer of n_slots slots per tile: tile-major [tile][slot][1 KiB] (a
@@ -219,8 +244,12 @@ struct DumpAddr {
   int64_t tile;
   int c, hh;
   int n_slots;  // slots per tile of the buffer
-  __device__ __forceinline__ char* at(int slot) const {
-    return base + dump_off(slot, tile, n_tiles, n_slots) + dump_lane_off(slot, c, hh);
+  // scalar base of the slot's 4 KiB group (`tile` is wave-uniform, the slot a compile-time constant at every call) +
+  // 32-bit lane offset + the slot's offset inside the group, which fits the store's immediate
+  __device__ __forceinline__ gchar* at(int slot) const {
+    const int slot0 = n_slots > 0 ? (slot & ~3) : slot;
+    gchar* group = uniform_global(base + dump_off(slot0, tile, n_tiles, n_slots));
+    return group + (unsigned)((slot - slot0) * kFragBytes + dump_lane_off(slot, c, hh));
   }
   // one fragment of this tile, non-temporal
   __device__ __forceinline__ void store(int slot, uint4 v) const { stream_store(at(slot), v); }
