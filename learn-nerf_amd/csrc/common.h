@@ -62,6 +62,14 @@ static int set_max_dynamic_lds(K kernel, int bytes) {
   return e == hipSuccess ? LNRF_OK : hip_fail(e, "hipFuncSetAttribute(max dynamic LDS)");
 }
 
+// compute units of the current device: the size of a persistent launch
+static inline int cu_count(int* cus) {
+  int dev = 0;
+  hipError_t e = hipGetDevice(&dev);
+  if (e == hipSuccess) e = hipDeviceGetAttribute(cus, hipDeviceAttributeMultiprocessorCount, dev);
+  return e == hipSuccess ? LNRF_OK : hip_fail(e, "hipDeviceGetAttribute(multiprocessor count)");
+}
+
 constexpr int kWave = 64;
 
 // ---- wave64 helpers -------------------------------------------------------

@@ -1,6 +1,7 @@
-// fused_chain.h — device building blocks shared by the fused MLP kernels (nerf_mlp.hip, ngp_mlp.hip):
-// the weight ring, accumulator <-> B-fragment conversion, dump addressing, the chain layer and the
-// split-K weight-gradient body.
+// fused_chain.h — device building blocks shared by the fused MLP kernels (nerf_mlp.hip, nerf_bwd_ls.hip,
+// refnerf_fused.hip, ngp_mlp.hip) and independent of the NeRF layout (that part is nerf_chain.h): the tile context, the
+// weight ring, bias staging, accumulator <-> B-fragment conversion in plain and split precision, ReLU masks,
+// dump addressing, the chain layer and the split-K weight-gradient body.
 #pragma once
 #include <utility>
 
@@ -58,6 +59,25 @@ struct Timeline {
 __device__ __forceinline__ bf16x8 bits_to_frag(uint4 v) { return __builtin_bit_cast(bf16x8, v); }
 __device__ __forceinline__ uint4 frag_to_bits(bf16x8 v) { return __builtin_bit_cast(uint4, v); }
 __device__ __forceinline__ bf16x8 zero_frag() { return bits_to_frag(make_uint4(0, 0, 0, 0)); }
+
+// One wave owns one 32-evaluation tile: lane = (column c of the tile, lane half h), evaluation m, valid = m exists.
+// `wave` is uniform (readfirstlane), so everything derived from `tile` stays in scalar registers.
+struct TileCtx {
+  int lane, wave, c, h;
+  int64_t tile, m;
+  bool valid;
+};
+// the tile of this wave in a launch of one workgroup of NW waves per NW tiles, M evaluations in all
+template <int NW>
+__device__ __forceinline__ TileCtx tile_ctx(int64_t M) {
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int c = lane & 31, h = lane >> 5;
+  const int64_t tile = (int64_t)blockIdx.x * NW + wave;
+  const int64_t m = tile * kTileCols + c;
+  return {lane, wave, c, h, tile, m, m < M};
+}
 
 // A wave-uniform global address pinned to a scalar register pair.  The empty asm hides the sum from the optimiser:
 // without it the compiler folds a slot's constant offset (slots are 1 KiB apart, the instruction's immediate reaches
@@ -154,7 +174,16 @@ struct Ring {
   }
 };
 
-// accumulator initialised with the fp32 bias of rows 32*o.. (LDS block, broadcast reads)
+// n fp32 biases, global -> the LDS block bias_acc() reads, by the NT threads of the workgroup (the caller's barrier
+// publishes them)
+template <int NT>
+__device__ __forceinline__ void stage_bias(const char* bias_g, int n) {
+  const float* src = reinterpret_cast<const float*>(bias_g);
+  float* dst = reinterpret_cast<float*>(&smem[kBiasLdsOff]);
+  for (int i = threadIdx.x; i < n; i += NT) dst[i] = src[i];
+}
+// accumulator initialised with the fp32 bias of rows bias_row0.. (LDS block, broadcast reads): register q holds row
+// (q & 3) + 8 (q >> 2) + 4 h of the tile
 __device__ __forceinline__ f32x16 bias_acc(int bias_row0, int h) {
   f32x16 acc;
   const float* b = reinterpret_cast<const float*>(&smem[kBiasLdsOff]) + bias_row0 + 4 * h;
@@ -222,6 +251,14 @@ __device__ __forceinline__ bf16x8 masked_frag(const f32x16& acc, unsigned bits, 
   return f;
 }
 
+// accumulator tile -> 32 columns of the row-major fp32 row of this lane's evaluation (`row` points at the tile's first
+// column): lane half h writes columns 4 h + 8 g .. + 3, g = 0..3
+__device__ __forceinline__ void store_tile_row(float* row, int h, const f32x16& acc) {
+  float* zr = row + 4 * h;
+#pragma unroll
+  for (int g = 0; g < 4; ++g)
+    *reinterpret_cast<float4*>(zr + 8 * g) = make_float4(acc[4 * g], acc[4 * g + 1], acc[4 * g + 2], acc[4 * g + 3]);
+}
 // the activation / gradient dumps are written once and read by a later kernel: non-temporal stores keep
 // them from displacing the L2-resident weight stream
 __device__ __forceinline__ void stream_store(gchar* p, uint4 v) {
@@ -254,6 +291,14 @@ struct DumpAddr {
   // one fragment of this tile, non-temporal
   __device__ __forceinline__ void store(int slot, uint4 v) const { stream_store(at(slot), v); }
 };
+// A ReLU-mask slot of a dump keeps one uint4 per lane at lane * 16 (mask_at): bit 16 o + q of the 128 <=> accumulator
+// register q of out tile o passed the ReLU.  mask_word: the 32 bits that hold out tile o (masked_frag shift 16 (o & 1)).
+__device__ __forceinline__ uint4* mask_at(const char* buf, int slot, int64_t tile, int64_t n_tiles, int n_slots, int lane) {
+  return reinterpret_cast<uint4*>(const_cast<char*>(buf) + dump_off(slot, tile, n_tiles, n_slots) + lane * 16);
+}
+__device__ __forceinline__ unsigned mask_word(const uint4& mk, int o) {
+  return (o >> 1) == 0 ? mk.x : ((o >> 1) == 1 ? mk.y : ((o >> 1) == 2 ? mk.z : mk.w));
+}
 // slots per tile of the operand buffers of a weight-gradient launch
 struct WgLayout {
   int x_slots, y_slots;
@@ -305,6 +350,15 @@ __device__ __forceinline__ void split_store(float v, bf16x8& hi, bf16x8& lo, int
   lo[j] = (__bf16)(v - (float)hb);
 }
 
+// pack kernels: the parameter an index map (nerf_layout.h pack walks) names, 0 for padding (idx < 0)
+__device__ __forceinline__ float param_or_zero(const float* params, int64_t idx) {
+  return idx >= 0 ? params[idx] : 0.0f;
+}
+// what a split stream stores for weight w in its hi / lo fragment
+__device__ __forceinline__ __bf16 split_half(float w, bool lo_part) {
+  const __bf16 hi = (__bf16)w;
+  return lo_part ? (__bf16)(w - (float)hi) : hi;
+}
 // one GEMM layer with split operands; C0 = consumption index (in hi/lo pairs) of the layer's first k-step
 template <int C0, int NK, int NO, class RING, class Init, class GetHi, class GetLo, class Epi>
 __device__ __forceinline__ void chain_layer_split(RING& ring, Init init, GetHi bhi, GetLo blo, Epi epi) {

@@ -59,36 +59,40 @@ int lnrf_host_fwd_layer_info(int s, int what) {
 int lnrf_host_bwd_layer_info(int t, int what) {
   return what == 0 ? bwd_nk(t) : what == 1 ? bwd_no(t) : what == 2 ? bwd_base(t) : bwd_dense(t);
 }
-// parameter index (or -1) feeding element j of lane `lane` of stream fragment g
-int lnrf_host_fwd_weight_index(int g, int lane, int j) {
-  int s = 0;
-  for (int i = 1; i < kFwdLayers; ++i)
-    if (g >= fwd_base(i)) s = i;
-  const int loc = g - fwd_base(s);
-  if (loc >= fwd_nk(s) * fwd_no(s)) return -1;
-  return fwd_weight_index(s, loc / fwd_nk(s), loc % fwd_nk(s), lane, j);
-}
-int lnrf_host_bwd_weight_index(int g, int lane, int j) {
-  int t = 0;
-  for (int i = 1; i < kBwdLayers; ++i)
-    if (g >= bwd_base(i)) t = i;
-  const int loc = g - bwd_base(t);
-  if (loc >= bwd_nk(t) * bwd_no(t)) return -1;
-  return bwd_weight_index(t, loc / bwd_nk(t), loc % bwd_nk(t), lane, j);
-}
-int lnrf_host_fwd_bias_index(int i) {
-  int s = 0;
-  for (int k = 1; k < kFwdLayers; ++k)
-    if (i >= fwd_bias_base(k)) s = k;
-  return fwd_bias_index(s, i - fwd_bias_base(s));
-}
+// parameter index (or -1) feeding element j of lane `lane` of stream fragment g: the pack walks of nerf_layout.h
+int lnrf_host_fwd_weight_index(int g, int lane, int j) { return fwd_stream_index(g, lane, j, false); }
+int lnrf_host_bwd_weight_index(int g, int lane, int j) { return bwd_stream_index(g, lane, j, false); }
+int lnrf_host_fwd_bias_index(int i) { return bias_block_index(i, false); }
 int lnrf_host_nrm_frags(void) { return kNrmFrags; }
-int lnrf_host_nrm_weight_index(int g, int lane, int j) {
-  int u = 0;
-  for (int i = 1; i < kNrmLayers; ++i)
-    if (g >= nrm_base(i)) u = i;
-  const int loc = g - nrm_base(u);
-  return nrm_weight_index(u, loc / nrm_nk(u), loc % nrm_nk(u), lane, j);
+int lnrf_host_nrm_weight_index(int g, int lane, int j) { return nrm_stream_index(g, lane, j); }
+// The index array of a whole stream, out[(g * 64 + lane) * 8 + j] (bias blocks: out[i]); returns its length, -1 for an
+// unknown stream.  stream 0 forward, 1 transposed, 2 split forward, 3 bias block (ref != 0: RefNERFModel's trunk-only
+// form of these four), 4 normal pass, 5 / 6 / 7 directional forward / transposed / bias block.  out == NULL: length only.
+int64_t lnrf_host_stream_indices(int stream, int ref, int32_t* out) {
+  const int frags[8] = {kFwdFrags, kBwdFrags, kFwd3Frags, 0, kNrmFrags, kDirFwdFrags, kDirBwdFrags, 0};
+  if (stream < 0 || stream > 7) return -1;
+  if (stream == 3 || stream == 7) {
+    const int n = stream == 3 ? kBiasFloats : kDirBiasFloats;
+    for (int i = 0; out && i < n; ++i) out[i] = stream == 3 ? bias_block_index(i, ref != 0) : dir_bias_index(i);
+    return n;
+  }
+  const int64_t n = (int64_t)frags[stream] * 512;
+  for (int64_t e = 0; out && e < n; ++e) {
+    const int g = (int)(e >> 9), lane = (int)((e >> 3) & 63), j = (int)(e & 7);
+    out[e] = stream == 0 ? fwd_stream_index(g, lane, j, ref != 0) : stream == 1 ? bwd_stream_index(g, lane, j, ref != 0)
+           : stream == 2 ? fwd3_stream_index(g, lane, j, ref != 0) : stream == 4 ? nrm_stream_index(g, lane, j)
+           : stream == 5 ? dir_fwd_weight_index(g, lane, j) : dir_bwd_weight_index(g, lane, j);
+  }
+  return n;
+}
+// byte offsets of the regions of the packed blobs.  what 0..3 NeRFModel: forward, transposed, bias, size | 4, 5 its split
+// blob: bias, size | 6..10 RefNERFModel behind the NeRFModel regions: normal pass, directional forward / transposed / bias,
+// size | 11..16 its split blob: forward, bias, normal pass, directional forward, directional bias, size
+int64_t lnrf_host_pack_offset(int what) {
+  const int64_t v[17] = {kPackFwdOff, kPackBwdOff, kPackBiasOff, kPackBytes, kPack3BiasOff, kPack3Bytes,
+                         kRefPackNrmOff, kRefPackDirFwdOff, kRefPackDirBwdOff, kRefPackDirBiasOff, kRefPackBytes,
+                         kRef3FwdOff, kRef3BiasOff, kRef3NrmOff, kRef3DirOff, kRef3DirBiasOff, kRef3Bytes};
+  return what >= 0 && what < 17 ? v[what] : -1;
 }
 int lnrf_host_xemb_feat(int ks, int h, int j) { return xemb_feat(ks, h, j); }
 // slot orders of the save / gradient-dump tiles: what 0 x_emb, 1 h_l (arg = l), 2 z, 3 d_emb, 4 h10, 5 masks, 6 slots per tile

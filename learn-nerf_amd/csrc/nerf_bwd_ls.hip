@@ -539,10 +539,8 @@ extern "C" int lnrf_debug_set_ls_timeline(void* buf) {
 constexpr int kLsMaxPipelines = 64;
 // pipelines of a launch (one per 8 CUs), at least `need`
 static int ls_pipelines_for_device(int need, int* out) {
-  int dev = 0, cus = 0;
-  hipError_t e = hipGetDevice(&dev);
-  if (e == hipSuccess) e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-  if (e != hipSuccess) return hip_fail(e, "hipDeviceGetAttribute(multiprocessor count)");
+  int cus = 0;
+  if (int rc = cu_count(&cus)) return rc;
   *out = cus / kLsStages < kLsMaxPipelines ? cus / kLsStages : kLsMaxPipelines;
   if (*out < need) {
     set_error("layer-stationary backward: the device has too few CUs for a pipeline of 8 per model");

@@ -1,10 +1,96 @@
-// nerf_chain.h — parts of the NeRFModel backward shared by nerf_mlp.hip (separate chain / weight-gradient launches),
-// nerf_bwd_ls.hip (layer-stationary backward) and refnerf_fused.hip: the input-gradient chain of one 32-evaluation
-// tile and the launch of the weight-gradient problems of nerf_wgrad.h.
+// nerf_chain.h — the pieces of the NeRFModel trunk (nerf_layout.h) shared by nerf_mlp.hip, nerf_bwd_ls.hip (layer-stationary
+// backward) and refnerf_fused.hip: the positional encoding of x, the trunk layer of the forward / tangent chains, the masked
+// step of the input-gradient chains, the input-gradient chain of one 32-evaluation tile and the launch of the
+// weight-gradient problems of nerf_wgrad.h.
 #pragma once
 #include "fused_chain.h"
 
 namespace lnrf {
+
+// Positional encoding (model.py:65-77, fp32) of x into the 4 fragments of x_emb: a lane half holds kXPairs (coordinate,
+// frequency) pairs, four per k-step, numbered pg = kXPairs * h + p = kXFreqs * coordinate + frequency over both halves;
+// pair p = kXPairs is zero padding (the map of nerf_layout.h xemb_feat).  put(ks_, j, value) receives element j of
+// fragment ks_: sin in 2 pp, cos in 2 pp + 1 of pair pp, and stores it as bf16 or as a hi / lo pair.
+// The pair arithmetic is spelled out: behind a function shared with xemb_feat the kernels compile to different code.
+template <class Put>
+__device__ __forceinline__ void x_encode(const float (&px)[3], int h, Put put) {
+  static_for<4>([&](auto ks_) {
+    constexpr int ks = decltype(ks_)::value;
+#pragma unroll
+    for (int pp = 0; pp < 4; ++pp) {
+      const int p = 4 * ks + pp;
+      float s = 0.0f, co = 0.0f;
+      if (p < kXPairs) {
+        const int pg = kXPairs * h + p;
+        const int cd = pg / kXFreqs, f = pg - kXFreqs * cd;
+        const float v = cd == 0 ? px[0] : (cd == 1 ? px[1] : px[2]);
+        sincos_pe(v * (float)(1 << f), &s, &co);
+      }
+      put(ks_, 2 * pp, s);
+      put(ks_, 2 * pp + 1, co);
+    }
+  });
+}
+
+// One layer S of the trunk on the forward weight stream: B operand = x_emb for Dense_0, the previous layer's 16
+// fragments after that (+ x_emb as k-steps 16..19 of Dense_5, model.py:52).  BIAS: accumulators start from the bias
+// (forward) or from zero (tangent chain).  epi(o_, acc) per out tile.
+template <int S, bool BIAS, class RING, class Epi>
+__device__ __forceinline__ void trunk_layer(RING& ring, int h, const bf16x8 (&xe)[4], const bf16x8 (&in)[16], Epi epi) {
+  chain_layer<fwd_cons_base(S), fwd_nk(S), fwd_no(S)>(
+      ring,
+      [&](auto o_) {
+        if constexpr (BIAS) return bias_acc(fwd_bias_base(S) + 32 * decltype(o_)::value, h);
+        else return zero_acc();
+      },
+      [&](auto k_) -> bf16x8 {
+        constexpr int ks = decltype(k_)::value;
+        if constexpr (S == 0) return xe[ks];
+        else if constexpr (ks < 16) return in[ks];
+        else return xe[ks - 16];
+      },
+      epi);
+}
+// ... in split precision (always with bias)
+template <int S, class RING, class Epi>
+__device__ __forceinline__ void trunk_layer_split(RING& ring, int h, const bf16x8 (&xe_hi)[4], const bf16x8 (&xe_lo)[4],
+                                                  const bf16x8 (&inh)[16], const bf16x8 (&inl)[16], Epi epi) {
+  chain_layer_split<fwd_cons_base(S), fwd_nk(S), fwd_no(S)>(
+      ring, [&](auto o_) { return bias_acc(fwd_bias_base(S) + 32 * decltype(o_)::value, h); },
+      [&](auto k_) -> bf16x8 {
+        constexpr int ks = decltype(k_)::value;
+        if constexpr (S == 0) return xe_hi[ks];
+        else if constexpr (ks < 16) return inh[ks];
+        else return xe_hi[ks - 16];
+      },
+      [&](auto k_) -> bf16x8 {
+        constexpr int ks = decltype(k_)::value;
+        if constexpr (S == 0) return xe_lo[ks];
+        else if constexpr (ks < 16) return inl[ks];
+        else return xe_lo[ks - 16];
+      },
+      epi);
+}
+// Epilogue of a masked step: out tile o of `acc` times the ReLU mask `mk` -> fragments 2 o, 2 o + 1 of `out`, dumped to
+// slots slot0 + 2 o, + 1 of `gd`
+template <int O>
+__device__ __forceinline__ void masked_out_tile(const f32x16& acc, const uint4& mk, bf16x8 (&out)[16], const DumpAddr& gd,
+                                                int slot0) {
+  const unsigned mb = mask_word(mk, O);
+  out[2 * O] = masked_frag<0>(acc, mb, 16 * (O & 1));
+  out[2 * O + 1] = masked_frag<1>(acc, mb, 16 * (O & 1));
+  gd.store(slot0 + 2 * O, frag_to_bits(out[2 * O]));
+  gd.store(slot0 + 2 * O + 1, frag_to_bits(out[2 * O + 1]));
+}
+// One hidden step of an input-gradient chain (256 x 256 layer whose fragments start at consumption index C0):
+// out = relu'(h_{L-1}) * (W_L^T in), dumped as dy_{L-1} / c_{L-1}
+template <int C0, int L, class RING>
+__device__ __forceinline__ void hidden_back(RING& ring, bf16x8 (&in)[16], bf16x8 (&out)[16], const uint4& mk,
+                                            const DumpAddr& gd) {
+  chain_layer<C0, 16, 8>(
+      ring, [&](auto) { return zero_acc(); }, [&](auto k_) -> bf16x8 { return in[decltype(k_)::value]; },
+      [&](auto o_, const f32x16& acc) { masked_out_tile<decltype(o_)::value>(acc, mk, out, gd, grad_dy_slot(L - 1)); });
+}
 
 struct BwdSeq {
   static constexpr int count = kBwdUsed;
@@ -40,8 +126,7 @@ __device__ __forceinline__ void bwd_chain_tile(RING& ring, const DumpAddr& gd, c
   uint4 relu_mask[9];
 #pragma unroll
   for (int i = HEAD_ONLY ? 8 : 0; i < 9; ++i)  // the head launch only applies relu'(h10)
-    relu_mask[i] = *reinterpret_cast<const uint4*>(save + dump_off(kSaveMask + i, tile, save_tiles, kSaveTileSlots) +
-                                                   lane * 16);
+    relu_mask[i] = *mask_at(save, kSaveMask + i, tile, save_tiles, kSaveTileSlots, lane);
   __syncthreads();
   ring.prologue();
   LNRF_TL_STAMP(ring);
@@ -60,12 +145,7 @@ __device__ __forceinline__ void bwd_chain_tile(RING& ring, const DumpAddr& gd, c
   chain_layer<bwd_cons_base(0), bwd_nk(0), bwd_no(0)>(
       ring, [&](auto) { return zero_acc(); }, [&](auto) -> bf16x8 { return dy11; },
       [&](auto o_, const f32x16& acc) {
-        constexpr int o = decltype(o_)::value;
-        const unsigned mb = (o >> 1) == 0 ? relu_mask[8].x : relu_mask[8].y;
-        a0[2 * o] = masked_frag<0>(acc, mb, 16 * (o & 1));
-        a0[2 * o + 1] = masked_frag<1>(acc, mb, 16 * (o & 1));
-        gd.store(kGradDy10m + 2 * o, frag_to_bits(a0[2 * o]));
-        gd.store(kGradDy10m + 2 * o + 1, frag_to_bits(a0[2 * o + 1]));
+        masked_out_tile<decltype(o_)::value>(acc, relu_mask[8], a0, gd, kGradDy10m);
       });
   // logit-gradient fragment: slot (h=0, j=0)
   bf16x8 dlogit = zero_frag();
@@ -91,30 +171,12 @@ __device__ __forceinline__ void bwd_chain_tile(RING& ring, const DumpAddr& gd, c
 
   if constexpr (HEAD_ONLY) return;
   // T2..T9: Dense_l^T for l = 8..1: dy_l (in) -> dh_{l-1}, masked by relu(h_{l-1}) -> dy_{l-1}
-  auto back = [&](auto t_, bf16x8(&in)[16], bf16x8(&out)[16]) {
-    constexpr int TT = decltype(t_)::value;
-    constexpr int l = bwd_dense(TT);  // dense layer whose transpose is applied
-    chain_layer<bwd_cons_base(TT), bwd_nk(TT), bwd_no(TT)>(
-        ring, [&](auto) { return zero_acc(); },
-        [&](auto k_) -> bf16x8 { return in[decltype(k_)::value]; },
-        [&](auto o_, const f32x16& acc) {
-          constexpr int o = decltype(o_)::value;
-          const uint4 mk = relu_mask[l - 1];
-          const unsigned mb = (o >> 1) == 0 ? mk.x : ((o >> 1) == 1 ? mk.y : ((o >> 1) == 2 ? mk.z : mk.w));
-          out[2 * o] = masked_frag<0>(acc, mb, 16 * (o & 1));
-          out[2 * o + 1] = masked_frag<1>(acc, mb, 16 * (o & 1));
-          gd.store(grad_dy_slot(l - 1) + 2 * o, frag_to_bits(out[2 * o]));
-          gd.store(grad_dy_slot(l - 1) + 2 * o + 1, frag_to_bits(out[2 * o + 1]));
-        });
-  };
-  back(std::integral_constant<int, 2>{}, a1, a0);  // Dense_8^T: dy8 -> dy7
-  back(std::integral_constant<int, 3>{}, a0, a1);  // dy7 -> dy6
-  back(std::integral_constant<int, 4>{}, a1, a0);  // dy6 -> dy5
-  back(std::integral_constant<int, 5>{}, a0, a1);  // Dense_5^T (h rows): dy5 -> dy4
-  back(std::integral_constant<int, 6>{}, a1, a0);  // dy4 -> dy3
-  back(std::integral_constant<int, 7>{}, a0, a1);  // dy3 -> dy2
-  back(std::integral_constant<int, 8>{}, a1, a0);  // dy2 -> dy1
-  back(std::integral_constant<int, 9>{}, a0, a1);  // Dense_1^T: dy1 -> dy0
+  static_assert(bwd_nk(2) == 16 && bwd_no(2) == 8, "hidden_back");
+  static_for<8>([&](auto i_) {
+    constexpr int TT = 2 + decltype(i_)::value, l = bwd_dense(TT);  // dense layer whose transpose is applied: 8..1
+    if constexpr (TT % 2 == 0) hidden_back<bwd_cons_base(TT), l>(ring, a1, a0, relu_mask[l - 1], gd);
+    else hidden_back<bwd_cons_base(TT), l>(ring, a0, a1, relu_mask[l - 1], gd);
+  });
 }
 
 // launches nerf_wgrad_kernel (nerf_mlp.hip) on the workgroups of `list` (at most kWgradMaxBlocks): X operands from xbuf,

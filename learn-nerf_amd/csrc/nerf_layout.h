@@ -53,17 +53,19 @@ NL_HD constexpr int hidden_feat(int ks, int h, int j) { return 16 * ks + 8 * (j 
 // x embedding (60 features, model.py:72-77 order e = 20c + f [sin] / 20c + 10 + f [cos]) lives in
 // 4 k-steps: lane-half h holds 15 (coordinate, frequency) pairs p_global = 15h + p, p = 4ks + (j>>1),
 // element j&1 = {sin, cos}; p == 15 is padding.  Returns -1 for a pad slot.
+constexpr int kXPairs = 15, kXFreqs = 10;  // pairs per lane half, frequencies per coordinate
 NL_HD constexpr int xemb_feat(int ks, int h, int j) {
   const int p = 4 * ks + (j >> 1);
-  if (p >= 15) return -1;
-  const int pg = 15 * h + p;
+  if (p >= kXPairs) return -1;
+  const int pg = kXPairs * h + p;
   return 20 * (pg / 10) + (pg % 10) + 10 * (j & 1);
 }
 // d embedding (24 features, e = 8c + f / 8c + 4 + f) lives in 2 k-steps: 6 pairs per lane-half.
+constexpr int kDPairs = 6, kDFreqs = 4;
 NL_HD constexpr int demb_feat(int ks, int h, int j) {
   const int p = 4 * ks + (j >> 1);
-  if (p >= 6) return -1;
-  const int pg = 6 * h + p;
+  if (p >= kDPairs) return -1;
+  const int pg = kDPairs * h + p;
   return 8 * (pg / 4) + (pg % 4) + 4 * (j & 1);
 }
 
@@ -313,6 +315,62 @@ constexpr int64_t kRefPackDirFwdOff = kRefPackNrmOff + (int64_t)kNrmFrags * kFra
 constexpr int64_t kRefPackDirBwdOff = kRefPackDirFwdOff + (int64_t)kDirFwdFrags * kFragBytes;
 constexpr int64_t kRefPackDirBiasOff = kRefPackDirBwdOff + (int64_t)kDirBwdFrags * kFragBytes;
 constexpr int64_t kRefPackBytes = kRefPackDirBiasOff + 1024;
+// Ref-NeRF split-precision render blob: [hi, lo] pairs of the forward stream of Dense_0..8 | fp32 biases | pairs of the
+// normal-pass stream | pairs of the directional forward stream | its fp32 biases
+constexpr int kRef3FwdFrags = fwd3_base(9);
+constexpr int64_t kRef3FwdOff = 0;
+constexpr int64_t kRef3BiasOff = (int64_t)kRef3FwdFrags * kFragBytes;
+constexpr int64_t kRef3NrmOff = kRef3BiasOff + round_up(kBiasFloats * 4, 1024);
+constexpr int64_t kRef3DirOff = kRef3NrmOff + 2 * (int64_t)kNrmFrags * kFragBytes;
+constexpr int64_t kRef3DirBiasOff = kRef3DirOff + 2 * (int64_t)kDirFwdFrags * kFragBytes;
+constexpr int64_t kRef3Bytes = kRef3DirBiasOff + 1024;
+static_assert(kRef3FwdFrags % kStageFrags == 0 && (2 * kNrmFrags) % kStageFrags == 0 && (2 * kDirFwdFrags) % kStageFrags == 0,
+              "split streams are whole stages");
+
+// ---- pack walks ---------------------------------------------------------------------------------
+// Parameter index feeding element (lane, j) of fragment g of a whole stream (stage-alignment padding included), or
+// bias float i of the bias block; -1 = zero.  The pack kernels and the host library call these and nothing else.
+// ref: RefNERFModel shares only the trunk Dense_0..8 with NeRFModel, so its blobs keep forward stream layers <= 8 and
+// transposed stream layers >= 2 (Dense_8..1^T) and zero the rest.
+NL_HD constexpr int fwd_stream_index(int g, int lane, int j, bool ref) {
+  int s = 0;
+  for (int i = 1; i < kFwdLayers; ++i)
+    if (g >= fwd_base(i)) s = i;
+  const int loc = g - fwd_base(s), nk = fwd_nk(s);
+  if (loc >= nk * fwd_no(s) || (ref && s > 8)) return -1;
+  return fwd_weight_index(s, loc / nk, loc % nk, lane, j);
+}
+NL_HD constexpr int bwd_stream_index(int g, int lane, int j, bool ref) {
+  int t = 0;
+  for (int i = 1; i < kBwdLayers; ++i)
+    if (g >= bwd_base(i)) t = i;
+  const int loc = g - bwd_base(t), nk = bwd_nk(t);
+  if (loc >= nk * bwd_no(t) || (ref && t < 2)) return -1;
+  return bwd_weight_index(t, loc / nk, loc % nk, lane, j);
+}
+NL_HD constexpr int nrm_stream_index(int g, int lane, int j) {  // Ref-NeRF only, no padding
+  int u = 0;
+  for (int i = 1; i < kNrmLayers; ++i)
+    if (g >= nrm_base(i)) u = i;
+  const int loc = g - nrm_base(u);
+  return nrm_weight_index(u, loc / nrm_nk(u), loc % nrm_nk(u), lane, j);
+}
+// split stream: fragments 2p and 2p + 1 of a layer are the hi and the lo half of pair p, which mirrors forward fragment
+// p of that layer.  In every split stream the half is the parity of the fragment (the layer bases are even).
+NL_HD constexpr int fwd3_stream_index(int g, int lane, int j, bool ref) {
+  int s = 0;
+  for (int i = 1; i < kFwdLayers; ++i)
+    if (g >= fwd3_base(i)) s = i;
+  const int pair = (g - fwd3_base(s)) >> 1, nk = fwd_nk(s);
+  if (pair >= nk * fwd_no(s) || (ref && s > 8)) return -1;
+  return fwd_weight_index(s, pair / nk, pair % nk, lane, j);
+}
+NL_HD constexpr int bias_block_index(int i, bool ref) {
+  int s = 0;
+  for (int k = 1; k < kFwdLayers; ++k)
+    if (i >= fwd_bias_base(k)) s = k;
+  return ref && s > 8 ? -1 : fwd_bias_index(s, i - fwd_bias_base(s));
+}
 
 // ---- saved activations / gradient dumps -------------------------------------------------------
 // Both buffers hold 1 KiB fragments addressed by (slot, tile) through dump_off() (tile-major [tile][slot]); a slot is one

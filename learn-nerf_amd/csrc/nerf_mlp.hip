@@ -4,7 +4,7 @@
 //            the f32 accumulator tile of layer l (32 out-features x 32 evaluations) is converted
 //            to bf16 in place and is the B operand of layer l+1 (nerf_layout.h).  Weights are
 //            pre-packed in MFMA A-fragment order and streamed L2 -> VGPR -> LDS through a
-//            two-slot ring of 16 KiB stages shared by the 8 waves (one barrier per stage).
+//            three-slot ring of 16 KiB stages shared by the 8 waves (one barrier per stage, fused_chain.h Ring).
 // Backward : (1) the same structure on the transposed weight stream produces the pre-activation
 //            gradients dy_l and dumps them, (2) a split-K MFMA kernel reduces
 //            dW_l = X_l^T dy_l over all evaluations from the forward/backward dumps.
@@ -35,20 +35,10 @@ __global__ __launch_bounds__(kThreads) void nerf_fwd_kernel(
     const char* __restrict__ packed, const float* __restrict__ xin_g, const float* __restrict__ din_g,
     const float* __restrict__ rays, int64_t ray_stride, const float* __restrict__ ts, int T, int64_t M,
     int64_t n_tiles, float* __restrict__ density, float* __restrict__ rgb, char* __restrict__ save) {
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int c = lane & 31, h = lane >> 5;
-  const int64_t tile = (int64_t)blockIdx.x * kWaves + wave;
-  const int64_t m = tile * kTileCols + c;
-  const bool valid = m < M;
+  const auto [lane, wave, c, h, tile, m, valid] = tile_ctx<kWaves>(M);
 
-  // biases -> LDS, inputs -> registers (all ordinary loads retire before the first LDS-DMA)
-  {
-    const float* bias_g = reinterpret_cast<const float*>(packed + kPackBiasOff);
-    float* bias_l = reinterpret_cast<float*>(&smem[kBiasLdsOff]);
-    for (int i = tid; i < kBiasFloats; i += kThreads) bias_l[i] = bias_g[i];
-  }
+  // biases -> LDS, inputs -> registers
+  stage_bias<kThreads>(packed + kPackBiasOff, kBiasFloats);
   float px[3] = {0, 0, 0}, pd[3] = {0, 0, 0};
   if (valid) {
     if (FROM_RAYS) {
@@ -85,22 +75,7 @@ __global__ __launch_bounds__(kThreads) void nerf_fwd_kernel(
 
   // positional encodings (model.py:65-77) in fp32, rounded to bf16 operands
   bf16x8 xe[4], de[2];
-  static_for<4>([&](auto ks_) {
-    constexpr int ks = decltype(ks_)::value;
-#pragma unroll
-    for (int pp = 0; pp < 4; ++pp) {
-      const int p = 4 * ks + pp;
-      float s = 0.0f, co = 0.0f;
-      if (p < 15) {
-        const int pg = 15 * h + p;
-        const int cd = pg / 10, f = pg - 10 * cd;
-        const float v = cd == 0 ? px[0] : (cd == 1 ? px[1] : px[2]);
-        sincos_pe(v * (float)(1 << f), &s, &co);
-      }
-      xe[ks][2 * pp] = (__bf16)s;
-      xe[ks][2 * pp + 1] = (__bf16)co;
-    }
-  });
+  x_encode(px, h, [&](auto ks_, int j, float v) { xe[decltype(ks_)::value][j] = (__bf16)v; });
   static_for<2>([&](auto ks_) {
     constexpr int ks = decltype(ks_)::value;
 #pragma unroll
@@ -134,25 +109,17 @@ __global__ __launch_bounds__(kThreads) void nerf_fwd_kernel(
   auto hidden = [&](auto s_, bf16x8(&in)[16], bf16x8(&out)[16], auto relu_, int save_slot) {
     constexpr int S = decltype(s_)::value;
     constexpr bool RELU = decltype(relu_)::value;
-    chain_layer<fwd_cons_base(S), fwd_nk(S), fwd_no(S)>(
-        ring, [&](auto o_) { return bias_acc(fwd_bias_base(S) + 32 * decltype(o_)::value, h); },
-        [&](auto k_) -> bf16x8 {
-          constexpr int ks = decltype(k_)::value;
-          if constexpr (S == 0) return xe[ks];
-          else if constexpr (ks < 16) return in[ks];
-          else return xe[ks - 16];
-        },
-        [&](auto o_, const f32x16& acc) {
-          constexpr int o = decltype(o_)::value;
-          out[2 * o] = acc_to_frag<0, RELU>(acc);
-          out[2 * o + 1] = acc_to_frag<1, RELU>(acc);
-          save_frag(save_slot + 2 * o, out[2 * o]);
-          save_frag(save_slot + 2 * o + 1, out[2 * o + 1]);
-          if constexpr (SAVE && RELU && HMASKS)
-            mask_bits[o >> 1] |= relu_bits(out[2 * o], out[2 * o + 1]) << (16 * (o & 1));
-        });
+    trunk_layer<S, true>(ring, h, xe, in, [&](auto o_, const f32x16& acc) {
+      constexpr int o = decltype(o_)::value;
+      out[2 * o] = acc_to_frag<0, RELU>(acc);
+      out[2 * o + 1] = acc_to_frag<1, RELU>(acc);
+      save_frag(save_slot + 2 * o, out[2 * o]);
+      save_frag(save_slot + 2 * o + 1, out[2 * o + 1]);
+      if constexpr (SAVE && RELU && HMASKS)
+        mask_bits[o >> 1] |= relu_bits(out[2 * o], out[2 * o + 1]) << (16 * (o & 1));
+    });
     if constexpr (SAVE && RELU && HMASKS) {
-      *reinterpret_cast<uint4*>(save + dump_off(kSaveMask + S, tile, n_tiles, kSaveTileSlots) + lane * 16) =
+      *mask_at(save, kSaveMask + S, tile, n_tiles, kSaveTileSlots, lane) =
           make_uint4(mask_bits[0], mask_bits[1], mask_bits[2], mask_bits[3]);
       mask_bits[0] = mask_bits[1] = mask_bits[2] = mask_bits[3] = 0u;
     }
@@ -186,10 +153,8 @@ __global__ __launch_bounds__(kThreads) void nerf_fwd_kernel(
           save_frag(kSaveH10 + 2 * o + 1, a1[2 * o + 1]);
           if constexpr (SAVE) mask_bits[o >> 1] |= relu_bits(a1[2 * o], a1[2 * o + 1]) << (16 * (o & 1));
         } else {
-          if constexpr (SAVE) {
-            *reinterpret_cast<uint4*>(save + dump_off(kSaveMask + 8, tile, n_tiles, kSaveTileSlots) +
-                                      lane * 16) = make_uint4(mask_bits[0], mask_bits[1], 0u, 0u);
-          }
+          if constexpr (SAVE)
+            *mask_at(save, kSaveMask + 8, tile, n_tiles, kSaveTileSlots, lane) = make_uint4(mask_bits[0], mask_bits[1], 0u, 0u);
           if (h == 0 && valid) {
             const float x = acc[0];
             density[m] = fmaxf(x, 0.0f) + log1pf(expf(-fabsf(x)));  // softplus (model.py:57)
@@ -227,19 +192,9 @@ __global__ __launch_bounds__(kSplitThreads) void nerf_fwd_split_kernel(
     const char* __restrict__ packed, const float* __restrict__ xin_g, const float* __restrict__ din_g,
     const float* __restrict__ rays, int64_t ray_stride, const float* __restrict__ ts, int T, int64_t M,
     float* __restrict__ density, float* __restrict__ rgb) {
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int c = lane & 31, h = lane >> 5;
-  const int64_t tile = (int64_t)blockIdx.x * kSplitWaves + wave;
-  const int64_t m = tile * kTileCols + c;
-  const bool valid = m < M;
+  const auto [lane, wave, c, h, tile, m, valid] = tile_ctx<kSplitWaves>(M);
 
-  {
-    const float* bias_g = reinterpret_cast<const float*>(packed + kPack3BiasOff);
-    float* bias_l = reinterpret_cast<float*>(&smem[kBiasLdsOff]);
-    for (int i = tid; i < kBiasFloats; i += kSplitThreads) bias_l[i] = bias_g[i];
-  }
+  stage_bias<kSplitThreads>(packed + kPack3BiasOff, kBiasFloats);
   float px[3] = {0, 0, 0}, pd[3] = {0, 0, 0};
   if (valid) {
     if (FROM_RAYS) {
@@ -269,22 +224,7 @@ __global__ __launch_bounds__(kSplitThreads) void nerf_fwd_split_kernel(
 
   // positional encodings (model.py:65-77) in fp32, split into bf16 pairs
   bf16x8 xe_hi[4], xe_lo[4], de_hi[2], de_lo[2];
-  static_for<4>([&](auto ks_) {
-    constexpr int ks = decltype(ks_)::value;
-#pragma unroll
-    for (int pp = 0; pp < 4; ++pp) {
-      const int p = 4 * ks + pp;
-      float s = 0.0f, co = 0.0f;
-      if (p < 15) {
-        const int pg = 15 * h + p;
-        const int cd = pg / 10, f = pg - 10 * cd;
-        const float v = cd == 0 ? px[0] : (cd == 1 ? px[1] : px[2]);
-        sincos_pe(v * (float)(1 << f), &s, &co);
-      }
-      split_store(s, xe_hi[ks], xe_lo[ks], 2 * pp);
-      split_store(co, xe_hi[ks], xe_lo[ks], 2 * pp + 1);
-    }
-  });
+  x_encode(px, h, [&](auto ks_, int j, float v) { split_store(v, xe_hi[decltype(ks_)::value], xe_lo[decltype(ks_)::value], j); });
   static_for<2>([&](auto ks_) {
     constexpr int ks = decltype(ks_)::value;
 #pragma unroll
@@ -305,27 +245,12 @@ __global__ __launch_bounds__(kSplitThreads) void nerf_fwd_split_kernel(
   bf16x8 a0h[16], a0l[16], a1h[16], a1l[16];
 
   auto hidden = [&](auto s_, bf16x8(&inh)[16], bf16x8(&inl)[16], bf16x8(&outh)[16], bf16x8(&outl)[16], auto relu_) {
-    constexpr int S = decltype(s_)::value;
     constexpr bool RELU = decltype(relu_)::value;
-    chain_layer_split<fwd_cons_base(S), fwd_nk(S), fwd_no(S)>(
-        ring, [&](auto o_) { return bias_acc(fwd_bias_base(S) + 32 * decltype(o_)::value, h); },
-        [&](auto k_) -> bf16x8 {
-          constexpr int ks = decltype(k_)::value;
-          if constexpr (S == 0) return xe_hi[ks];
-          else if constexpr (ks < 16) return inh[ks];
-          else return xe_hi[ks - 16];
-        },
-        [&](auto k_) -> bf16x8 {
-          constexpr int ks = decltype(k_)::value;
-          if constexpr (S == 0) return xe_lo[ks];
-          else if constexpr (ks < 16) return inl[ks];
-          else return xe_lo[ks - 16];
-        },
-        [&](auto o_, const f32x16& acc) {
-          constexpr int o = decltype(o_)::value;
-          acc_to_frag_split<0, RELU>(acc, outh[2 * o], outl[2 * o]);
-          acc_to_frag_split<1, RELU>(acc, outh[2 * o + 1], outl[2 * o + 1]);
-        });
+    trunk_layer_split<decltype(s_)::value>(ring, h, xe_hi, xe_lo, inh, inl, [&](auto o_, const f32x16& acc) {
+      constexpr int o = decltype(o_)::value;
+      acc_to_frag_split<0, RELU>(acc, outh[2 * o], outl[2 * o]);
+      acc_to_frag_split<1, RELU>(acc, outh[2 * o + 1], outl[2 * o + 1]);
+    });
   };
   std::true_type relu;
   std::false_type lin;
@@ -383,10 +308,7 @@ __global__ __launch_bounds__(kThreads) void nerf_bwd_chain_kernel(
     const char* __restrict__ packed, const char* __restrict__ save, const float* __restrict__ density,
     const float* __restrict__ rgb, const float* __restrict__ g_density, const float* __restrict__ g_rgb,
     int64_t M, int64_t n_tiles, char* __restrict__ gdump) {
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int64_t tile = (int64_t)blockIdx.x * kWaves + wave;
+  const auto [lane, wave, c, h, tile, m, valid] = tile_ctx<kWaves>(M);
 
   Ring<kBwdStages, BwdSeq> ring;
   ring.stream = packed + kPackBwdOff;
@@ -398,7 +320,7 @@ __global__ __launch_bounds__(kThreads) void nerf_bwd_chain_kernel(
   ring.tl.on = g_timeline_buf != nullptr && blockIdx.x == gridDim.x / 2;
   ring.tl.stamp();
 #endif
-  const DumpAddr gd{gdump, n_tiles, tile, lane & 31, lane >> 5, kGradTileSlots};
+  const DumpAddr gd{gdump, n_tiles, tile, c, h, kGradTileSlots};
   bwd_chain_tile(ring, gd, save, n_tiles, density, rgb, g_density, g_rgb, M, tile, lane);
 }
 
@@ -447,7 +369,8 @@ __global__ __launch_bounds__(64 * kSlabReduceWaves) void nerf_wgrad_reduce_kerne
 // ---------------------------------------------------------------------------------------------
 // weight packing
 // ---------------------------------------------------------------------------------------------
-// One thread per lane slot of a fragment (8 bf16 = one 16-byte store) or per bias float.
+// One thread per lane slot of a fragment (8 bf16 = one 16-byte store) or per bias float; the maps are the pack walks of
+// nerf_layout.h.
 __global__ void nerf_pack_kernel(const float* __restrict__ params, char* __restrict__ packed) {
   constexpr int64_t units_f = (int64_t)kFwdFrags * 64, units_b = (int64_t)kBwdFrags * 64;
   constexpr int64_t total = units_f + units_b + kBiasFloats;
@@ -456,32 +379,14 @@ __global__ void nerf_pack_kernel(const float* __restrict__ params, char* __restr
       const bool fwd = u < units_f;
       const int64_t uu = fwd ? u : u - units_f;
       const int g = (int)(uu >> 6), lane = (int)(uu & 63);
-      int layer = 0, loc, nk, n_used;
-      if (fwd) {
-        for (int i = 1; i < kFwdLayers; ++i)
-          if (g >= fwd_base(i)) layer = i;
-        loc = g - fwd_base(layer); nk = fwd_nk(layer); n_used = nk * fwd_no(layer);
-      } else {
-        for (int i = 1; i < kBwdLayers; ++i)
-          if (g >= bwd_base(i)) layer = i;
-        loc = g - bwd_base(layer); nk = bwd_nk(layer); n_used = nk * bwd_no(layer);
-      }
       bf16x8 out;
 #pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        int idx = -1;
-        if (loc < n_used) idx = fwd ? fwd_weight_index(layer, loc / nk, loc % nk, lane, j)
-                                    : bwd_weight_index(layer, loc / nk, loc % nk, lane, j);
-        out[j] = (__bf16)(idx >= 0 ? params[idx] : 0.0f);
-      }
+      for (int j = 0; j < 8; ++j)
+        out[j] = (__bf16)param_or_zero(params, fwd ? fwd_stream_index(g, lane, j, false) : bwd_stream_index(g, lane, j, false));
       *reinterpret_cast<bf16x8*>(packed + (fwd ? kPackFwdOff : kPackBwdOff) + uu * 16) = out;
     } else {
       const int i = (int)(u - units_f - units_b);
-      int s = 0;
-      for (int k = 1; k < kFwdLayers; ++k)
-        if (i >= fwd_bias_base(k)) s = k;
-      const int idx = fwd_bias_index(s, i - fwd_bias_base(s));
-      reinterpret_cast<float*>(packed + kPackBiasOff)[i] = idx >= 0 ? params[idx] : 0.0f;
+      reinterpret_cast<float*>(packed + kPackBiasOff)[i] = param_or_zero(params, bias_block_index(i, false));
     }
   }
 }
@@ -494,25 +399,10 @@ __global__ void nerf_pack_split_kernel(const float* __restrict__ params, char* _
        e += (int64_t)gridDim.x * blockDim.x) {
     if (e < total_w) {
       const int g = (int)(e >> 9), lane = (int)((e >> 3) & 63), j = (int)(e & 7);
-      int s = 0;
-      for (int i = 1; i < kFwdLayers; ++i)
-        if (g >= fwd3_base(i)) s = i;
-      const int loc = g - fwd3_base(s);
-      int idx = -1;
-      if (loc < 2 * fwd_nk(s) * fwd_no(s)) {
-        const int pair = loc >> 1;
-        idx = fwd_weight_index(s, pair / fwd_nk(s), pair % fwd_nk(s), lane, j);
-      }
-      const float w = idx >= 0 ? params[idx] : 0.0f;
-      const __bf16 hi = (__bf16)w;
-      reinterpret_cast<__bf16*>(packed)[e] = (loc & 1) ? (__bf16)(w - (float)hi) : hi;
+      reinterpret_cast<__bf16*>(packed)[e] = split_half(param_or_zero(params, fwd3_stream_index(g, lane, j, false)), g & 1);
     } else {
       const int i = (int)(e - total_w);
-      int s = 0;
-      for (int k = 1; k < kFwdLayers; ++k)
-        if (i >= fwd_bias_base(k)) s = k;
-      const int idx = fwd_bias_index(s, i - fwd_bias_base(s));
-      reinterpret_cast<float*>(packed + kPack3BiasOff)[i] = idx >= 0 ? params[idx] : 0.0f;
+      reinterpret_cast<float*>(packed + kPack3BiasOff)[i] = param_or_zero(params, bias_block_index(i, false));
     }
   }
 }

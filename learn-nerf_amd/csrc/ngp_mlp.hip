@@ -165,12 +165,8 @@ __global__ __launch_bounds__(kThreads) void ngp_mlp_kernel(
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int c = lane & 31, h = lane >> 5;
-  {
-    const float* bias_g = reinterpret_cast<const float*>(packed + kNgpPackBiasOff);
-    float* bias_l = reinterpret_cast<float*>(&smem[kBiasLdsOff]);
-    for (int i = tid; i < kNgpBiasFloats; i += kThreads) bias_l[i] = bias_g[i];
-    if (tid < 16) s_lmax[tid] = 0u;
-  }
+  stage_bias<kThreads>(packed + kNgpPackBiasOff, kNgpBiasFloats);
+  if (tid < 16) s_lmax[tid] = 0u;
   // persistent accumulators of the backward.  The layers are dealt to the two halves of the workgroup so that a
   // wave carries at most three dW tiles (five would not fit next to the chain's fragments): waves 0-3 take
   // Dense_3 (slot 0), Dense_4 (slot 1), Dense_0 (slot 2); waves 4-7 take Dense_2 (slot 0), Dense_1 (slot 1).
@@ -581,9 +577,7 @@ __global__ void ngp_pack_split_kernel(const float* __restrict__ params, NgpOffse
       const int gg = e >> 9, lane = (e >> 3) & 63, j = e & 7;
       const int g = gg >> 1;
       const int64_t idx = g < ngp_fwd_count(ne) ? ngp_fwd_param_index(g, lane, j, off, lf, ne) : -1;
-      const float w = idx >= 0 ? params[idx] : 0.0f;
-      const __bf16 hi = (__bf16)w;
-      reinterpret_cast<__bf16*>(packed)[e] = (gg & 1) ? (__bf16)(w - (float)hi) : hi;
+      reinterpret_cast<__bf16*>(packed)[e] = split_half(param_or_zero(params, idx), gg & 1);
     } else {
       const int i = e - total_w;
       int l = 0;
@@ -592,21 +586,6 @@ __global__ void ngp_pack_split_kernel(const float* __restrict__ params, NgpOffse
       const int loc = i - ngp_bias_base(l);
       reinterpret_cast<float*>(packed + kNgpSplitBiasOff)[i] = loc < ngp_out_dim(l) ? params[off.b[l] + loc] : 0.0f;
     }
-  }
-}
-
-__device__ __forceinline__ void ngp_split(float v, bf16x8& hi, bf16x8& lo, int j) {
-  const __bf16 hb = (__bf16)v;
-  hi[j] = hb;
-  lo[j] = (__bf16)(v - (float)hb);
-}
-template <int S, bool RELU>
-__device__ __forceinline__ void ngp_acc_split(const f32x16& acc, bf16x8& hi, bf16x8& lo) {
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    float v = acc[8 * S + j];
-    if (RELU) v = __builtin_amdgcn_fmed3f(v, 0.0f, __builtin_inff());
-    ngp_split(v, hi, lo, j);
   }
 }
 
@@ -667,7 +646,7 @@ __global__ __launch_bounds__(kThreads) void ngp_mlp_fwd_split_kernel(
       for (int j = 0; j < 8; ++j) {
         const int feat = 16 * ks + 8 * (j >> 2) + 4 * h + (j & 3);
         const float v = (valid && feat < lf) ? enc_t[(int64_t)(feat < lf ? feat : lf - 1) * M + mm] : 0.0f;
-        ngp_split(v, ef_hi[ks], ef_lo[ks], j);
+        split_store(v, ef_hi[ks], ef_lo[ks], j);
       }
     });
     float pd[3] = {0, 0, 0};
@@ -689,7 +668,7 @@ __global__ __launch_bounds__(kThreads) void ngp_mlp_fwd_split_kernel(
           sincos_pe(x * (float)(1 << fr), &sn, &co);
           v = (e & 4) ? co : sn;
         }
-        ngp_split(v, de_hi[ks], de_lo[ks], j);
+        split_store(v, de_hi[ks], de_lo[ks], j);
       }
     });
     bf16x8 h0h[4], h0l[4], o16h, o16l, c1h[4], c1l[4], c2h[4], c2l[4];
@@ -701,14 +680,14 @@ __global__ __launch_bounds__(kThreads) void ngp_mlp_fwd_split_kernel(
           [&](auto k_) -> bf16x8 { return ef_lo[decltype(k_)::value]; },
           [&](auto o_, const f32x16& acc) {
             constexpr int o = decltype(o_)::value;
-            ngp_acc_split<0, true>(acc, h0h[2 * o], h0l[2 * o]);
-            ngp_acc_split<1, true>(acc, h0h[2 * o + 1], h0l[2 * o + 1]);
+            acc_to_frag_split<0, true>(acc, h0h[2 * o], h0l[2 * o]);
+            acc_to_frag_split<1, true>(acc, h0h[2 * o + 1], h0l[2 * o + 1]);
           });
     layer(std::integral_constant<int, ngp_fwd_base(1, NE)>{}, std::integral_constant<int, 4>{}, std::integral_constant<int, 1>{},
           ngp_bias_base(1), [&](auto k_) -> bf16x8 { return h0h[decltype(k_)::value]; },
           [&](auto k_) -> bf16x8 { return h0l[decltype(k_)::value]; },
           [&](auto, const f32x16& acc) {
-            ngp_acc_split<0, false>(acc, o16h, o16l);
+            acc_to_frag_split<0, false>(acc, o16h, o16l);
             logit = acc[0];
           });
     layer(std::integral_constant<int, ngp_fwd_base(2, NE)>{}, std::integral_constant<int, 3>{}, std::integral_constant<int, 2>{},
@@ -725,16 +704,16 @@ __global__ __launch_bounds__(kThreads) void ngp_mlp_fwd_split_kernel(
           },
           [&](auto o_, const f32x16& acc) {
             constexpr int o = decltype(o_)::value;
-            ngp_acc_split<0, true>(acc, c1h[2 * o], c1l[2 * o]);
-            ngp_acc_split<1, true>(acc, c1h[2 * o + 1], c1l[2 * o + 1]);
+            acc_to_frag_split<0, true>(acc, c1h[2 * o], c1l[2 * o]);
+            acc_to_frag_split<1, true>(acc, c1h[2 * o + 1], c1l[2 * o + 1]);
           });
     layer(std::integral_constant<int, ngp_fwd_base(3, NE)>{}, std::integral_constant<int, 4>{}, std::integral_constant<int, 2>{},
           ngp_bias_base(3), [&](auto k_) -> bf16x8 { return c1h[decltype(k_)::value]; },
           [&](auto k_) -> bf16x8 { return c1l[decltype(k_)::value]; },
           [&](auto o_, const f32x16& acc) {
             constexpr int o = decltype(o_)::value;
-            ngp_acc_split<0, true>(acc, c2h[2 * o], c2l[2 * o]);
-            ngp_acc_split<1, true>(acc, c2h[2 * o + 1], c2l[2 * o + 1]);
+            acc_to_frag_split<0, true>(acc, c2h[2 * o], c2l[2 * o]);
+            acc_to_frag_split<1, true>(acc, c2h[2 * o + 1], c2l[2 * o + 1]);
           });
     layer(std::integral_constant<int, ngp_fwd_base(4, NE)>{}, std::integral_constant<int, 4>{}, std::integral_constant<int, 1>{},
           ngp_bias_base(4), [&](auto k_) -> bf16x8 { return c2h[decltype(k_)::value]; },
@@ -781,7 +760,7 @@ __global__ void ngp_pack_kernel(const float* __restrict__ params, NgpOffsets off
         else if (row >= kNgpHidden) row = -1;
         if (row >= 0 && k < od) idx = off.w[l] + (int64_t)row * od + k;
       }
-      reinterpret_cast<__bf16*>(packed)[e] = (__bf16)(idx >= 0 ? params[idx] : 0.0f);
+      reinterpret_cast<__bf16*>(packed)[e] = (__bf16)param_or_zero(params, idx);
     } else {
       const int i = e - total_frag_elems;
       int l = 0;
@@ -813,6 +792,11 @@ static NgpOffsets ngp_offsets(const lnrf_ngp_mlp_desc* d) {
     off += ngp_out_dim(l);
   }
   return o;
+}
+// The kernels exist for NE = 1 and 2 k-steps of encoding (L*F <= 16 / <= 32): launch(integral_constant<int, NE>) -> rc
+template <class F>
+static int ngp_with_ne(const lnrf_ngp_mlp_desc* d, F&& launch) {
+  return d->enc_dim <= 16 ? launch(std::integral_constant<int, 1>{}) : launch(std::integral_constant<int, 2>{});
 }
 #define NGP_REQUIRE_SUPPORTED(fn)                                                                          \
   if (!ngp_supported(desc)) {                                                                              \
@@ -880,25 +864,19 @@ extern "C" int lnrf_ngp_mlp_fwd_split(const lnrf_ngp_mlp_desc* desc, const void*
   if (m == 0) return LNRF_OK;
   LNRF_CHECK_ARG(packed_split && enc_t && d && density && rgb, "null pointer");
   const int64_t n_tiles = padded_tiles(m);
-  int dev = 0, cus = 0;
-  hipError_t e = hipGetDevice(&dev);
-  if (e == hipSuccess) e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-  if (e != hipSuccess) return hip_fail(e, "hipDeviceGetAttribute(multiprocessor count)");
+  int cus = 0;
+  if (int rc = cu_count(&cus)) return rc;
   int64_t nb = n_tiles / kWaves;
   if (nb > 2 * (int64_t)cus) nb = 2 * (int64_t)cus;  // persistent: the stream is staged in LDS once per workgroup
   hipStream_t st = as_stream(stream);
-  int rc;
-  if (desc->enc_dim <= 16) {
-    rc = set_max_dynamic_lds(ngp_mlp_fwd_split_kernel<1>, kNgpSplitBytes);
-    if (rc) return rc;
-    hipLaunchKernelGGL((ngp_mlp_fwd_split_kernel<1>), dim3((unsigned)nb), dim3(kThreads), kNgpSplitBytes, st,
+  const int rc = ngp_with_ne(desc, [&](auto ne_) {
+    constexpr int NE = decltype(ne_)::value;
+    if (int rc = set_max_dynamic_lds(ngp_mlp_fwd_split_kernel<NE>, kNgpSplitBytes)) return rc;
+    hipLaunchKernelGGL((ngp_mlp_fwd_split_kernel<NE>), dim3((unsigned)nb), dim3(kThreads), kNgpSplitBytes, st,
                        (const char*)packed_split, enc_t, d, (int)desc->enc_dim, m, n_tiles, density, rgb);
-  } else {
-    rc = set_max_dynamic_lds(ngp_mlp_fwd_split_kernel<2>, kNgpSplitBytes);
-    if (rc) return rc;
-    hipLaunchKernelGGL((ngp_mlp_fwd_split_kernel<2>), dim3((unsigned)nb), dim3(kThreads), kNgpSplitBytes, st,
-                       (const char*)packed_split, enc_t, d, (int)desc->enc_dim, m, n_tiles, density, rgb);
-  }
+    return (int)LNRF_OK;
+  });
+  if (rc) return rc;
   LNRF_LAUNCH_CHECK();
   return LNRF_OK;
 }
@@ -912,18 +890,14 @@ extern "C" int lnrf_ngp_mlp_fwd(const lnrf_ngp_mlp_desc* desc, const void* packe
   const int64_t n_tiles = padded_tiles(m);
   const dim3 grid((unsigned)((n_tiles + kWaves - 1) / kWaves)), block(kThreads);
   hipStream_t st = as_stream(stream);
-  int rc;
-  if (desc->enc_dim <= 16) {
-    rc = set_max_dynamic_lds(ngp_mlp_kernel<1, false>, kNgpLds);
-    if (rc) return rc;
-    hipLaunchKernelGGL((ngp_mlp_kernel<1, false>), grid, block, kNgpLds, st, (const char*)packed, enc_t, d,
+  const int rc = ngp_with_ne(desc, [&](auto ne_) {
+    constexpr int NE = decltype(ne_)::value;
+    if (int rc = set_max_dynamic_lds(ngp_mlp_kernel<NE, false>, kNgpLds)) return rc;
+    hipLaunchKernelGGL((ngp_mlp_kernel<NE, false>), grid, block, kNgpLds, st, (const char*)packed, enc_t, d,
                        (int)desc->enc_dim, m, n_tiles, density, rgb, nullptr, nullptr, nullptr, nullptr);
-  } else {
-    rc = set_max_dynamic_lds(ngp_mlp_kernel<2, false>, kNgpLds);
-    if (rc) return rc;
-    hipLaunchKernelGGL((ngp_mlp_kernel<2, false>), grid, block, kNgpLds, st, (const char*)packed, enc_t, d,
-                       (int)desc->enc_dim, m, n_tiles, density, rgb, nullptr, nullptr, nullptr, nullptr);
-  }
+    return (int)LNRF_OK;
+  });
+  if (rc) return rc;
   LNRF_LAUNCH_CHECK();
   return LNRF_OK;
 }
@@ -938,7 +912,6 @@ extern "C" int lnrf_ngp_mlp_bwd(const lnrf_ngp_mlp_desc* desc, const void* packe
   LNRF_CHECK_ARG(packed && enc_t && d && g_density && g_rgb && scratch && g_enc_t && grads, "null pointer");
   const int64_t n_tiles = padded_tiles(m);
   hipStream_t st = as_stream(stream);
-  int rc;
   // per-workgroup rows of level maxima live behind the partial dW rows in the scratch buffer
   float* lmax_parts = level_absmax ? reinterpret_cast<float*>(reinterpret_cast<char*>(scratch) +
                                                               ngp_lmax_off(desc, n_tiles))
@@ -963,10 +936,8 @@ extern "C" int lnrf_ngp_mlp_bwd(const lnrf_ngp_mlp_desc* desc, const void* packe
   add(3, 4, 0, 16, 16, 16, 32, 16, 48, 16);
   add(4, 0, 0, lf < 16 ? lf : 16, 16, lf > 16 ? lf - 16 : 0, 0, 0, 0, 0);
   // one persistent workgroup per CU forms the weight gradients itself (no dumps, no second launch)
-  int dev = 0, cus = 0;
-  hipError_t e = hipGetDevice(&dev);
-  if (e == hipSuccess) e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-  if (e != hipSuccess) return hip_fail(e, "hipDeviceGetAttribute(multiprocessor count)");
+  int cus = 0;
+  if (int rc = cu_count(&cus)) return rc;
   int64_t nb = n_tiles / kWaves;
   if (nb > cus) nb = cus;
   if (nb > kNgpMaxPersistent) nb = kNgpMaxPersistent;
@@ -982,19 +953,15 @@ extern "C" int lnrf_ngp_mlp_bwd(const lnrf_ngp_mlp_desc* desc, const void* packe
   const int n_params = ngp_dense_params(desc);
   const int pstride = ngp_pstride(desc);
   float* wparts = reinterpret_cast<float*>(scratch);
-  if (desc->enc_dim <= 16) {
-    rc = set_max_dynamic_lds(ngp_mlp_kernel<1, true>, kNgpFusedLds);
-    if (rc) return rc;
-    hipLaunchKernelGGL((ngp_mlp_kernel<1, true>), pgrid, block, kNgpFusedLds, st, (const char*)packed, enc_t, d,
+  const int rc = ngp_with_ne(desc, [&](auto ne_) {
+    constexpr int NE = decltype(ne_)::value;
+    if (int rc = set_max_dynamic_lds(ngp_mlp_kernel<NE, true>, kNgpFusedLds)) return rc;
+    hipLaunchKernelGGL((ngp_mlp_kernel<NE, true>), pgrid, block, kNgpFusedLds, st, (const char*)packed, enc_t, d,
                        (int)desc->enc_dim, m, n_tiles, nullptr, nullptr, g_density, g_rgb, nullptr, g_enc_t,
                        lmax_parts, a, wparts, pstride, (int64_t)desc->dense_offset);
-  } else {
-    rc = set_max_dynamic_lds(ngp_mlp_kernel<2, true>, kNgpFusedLds);
-    if (rc) return rc;
-    hipLaunchKernelGGL((ngp_mlp_kernel<2, true>), pgrid, block, kNgpFusedLds, st, (const char*)packed, enc_t, d,
-                       (int)desc->enc_dim, m, n_tiles, nullptr, nullptr, g_density, g_rgb, nullptr, g_enc_t,
-                       lmax_parts, a, wparts, pstride, (int64_t)desc->dense_offset);
-  }
+    return (int)LNRF_OK;
+  });
+  if (rc) return rc;
   LNRF_LAUNCH_CHECK();
   hipLaunchKernelGGL(ngp_wparts_reduce_kernel, dim3((unsigned)((n_params + 31) / 32)), dim3(256), 0, st, wparts,
                      (int)nb, pstride, n_params, plan, grads + desc->dense_offset);

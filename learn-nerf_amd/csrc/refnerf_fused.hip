@@ -32,19 +32,15 @@ struct FwdPrefixSeq {  // the forward stream up to (not including) stream layer 
   static constexpr int at(int c) { return fwd_seq(c); }
 };
 
+// ReLU masks of h_0..h_7 (written by the trunk forward), 16 bytes per lane and layer
 __device__ __forceinline__ void load_relu_masks(uint4 (&mask)[8], const char* __restrict__ save, int64_t n_tiles,
                                                 int64_t tile, int lane) {
 #pragma unroll
-  for (int i = 0; i < 8; ++i)
-    mask[i] = *reinterpret_cast<const uint4*>(save + dump_off(kSaveMask + i, tile, n_tiles, kSaveTileSlots) + lane * 16);
+  for (int i = 0; i < 8; ++i) mask[i] = *mask_at(save, kSaveMask + i, tile, n_tiles, kSaveTileSlots, lane);
 }
-// ReLU mask of h_i (written by the trunk forward), 16 bytes per lane
-__device__ __forceinline__ uint4 load_relu_mask(int i, const char* __restrict__ save, int64_t n_tiles, int64_t tile,
-                                                int lane) {
-  return *reinterpret_cast<const uint4*>(save + dump_off(kSaveMask + i, tile, n_tiles, kSaveTileSlots) + lane * 16);
-}
-__device__ __forceinline__ unsigned mask_word(const uint4& mk, int o) {
-  return (o >> 1) == 0 ? mk.x : ((o >> 1) == 1 ? mk.y : ((o >> 1) == 2 ? mk.z : mk.w));
+// ... of h_i alone
+__device__ __forceinline__ uint4 load_relu_mask(int i, const char* save, int64_t n_tiles, int64_t tile, int lane) {
+  return *mask_at(save, kSaveMask + i, tile, n_tiles, kSaveTileSlots, lane);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -53,18 +49,8 @@ __device__ __forceinline__ unsigned mask_word(const uint4& mk, int o) {
 __global__ __launch_bounds__(kThreads) void refnerf_trunk_fwd_kernel(
     const char* __restrict__ packed, const float* __restrict__ xin_g, int64_t M, int64_t n_tiles,
     char* __restrict__ save, float* __restrict__ zout, int64_t ldz) {
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int c = lane & 31, h = lane >> 5;
-  const int64_t tile = (int64_t)blockIdx.x * kWaves + wave;
-  const int64_t m = tile * kTileCols + c;
-  const bool valid = m < M;
-  {
-    const float* bias_g = reinterpret_cast<const float*>(packed + kPackBiasOff);
-    float* bias_l = reinterpret_cast<float*>(&smem[kBiasLdsOff]);
-    for (int i = tid; i < kBiasFloats; i += kThreads) bias_l[i] = bias_g[i];
-  }
+  const auto [lane, wave, c, h, tile, m, valid] = tile_ctx<kWaves>(M);
+  stage_bias<kThreads>(packed + kPackBiasOff, kBiasFloats);
   float px[3] = {0, 0, 0};
   if (valid) {
 #pragma unroll
@@ -78,22 +64,7 @@ __global__ __launch_bounds__(kThreads) void refnerf_trunk_fwd_kernel(
   ring.prologue();
 
   bf16x8 xe[4];
-  static_for<4>([&](auto ks_) {
-    constexpr int ks = decltype(ks_)::value;
-#pragma unroll
-    for (int pp = 0; pp < 4; ++pp) {
-      const int p = 4 * ks + pp;
-      float s = 0.0f, co = 0.0f;
-      if (p < 15) {
-        const int pg = 15 * h + p;
-        const int cd = pg / 10, f = pg - 10 * cd;
-        const float v = cd == 0 ? px[0] : (cd == 1 ? px[1] : px[2]);
-        sincos_pe(v * (float)(1 << f), &s, &co);
-      }
-      xe[ks][2 * pp] = (__bf16)s;
-      xe[ks][2 * pp + 1] = (__bf16)co;
-    }
-  });
+  x_encode(px, h, [&](auto ks_, int j, float v) { xe[decltype(ks_)::value][j] = (__bf16)v; });
   DumpAddr dump{save, n_tiles, tile, c, h, kSaveTileSlots};
   static_for<4>([&](auto i) { stream_store(dump.at(kSaveXin + decltype(i)::value), frag_to_bits(xe[decltype(i)::value])); });
 
@@ -101,24 +72,15 @@ __global__ __launch_bounds__(kThreads) void refnerf_trunk_fwd_kernel(
   unsigned mask_bits[4] = {0u, 0u, 0u, 0u};
   auto hidden = [&](auto s_, bf16x8(&in)[16], bf16x8(&out)[16]) {
     constexpr int S = decltype(s_)::value;
-    chain_layer<fwd_cons_base(S), fwd_nk(S), fwd_no(S)>(
-        ring, [&](auto o_) { return bias_acc(fwd_bias_base(S) + 32 * decltype(o_)::value, h); },
-        [&](auto k_) -> bf16x8 {
-          constexpr int ks = decltype(k_)::value;
-          if constexpr (S == 0) return xe[ks];
-          else if constexpr (ks < 16) return in[ks];
-          else return xe[ks - 16];
-        },
-        [&](auto o_, const f32x16& acc) {
-          constexpr int o = decltype(o_)::value;
-          out[2 * o] = acc_to_frag<0, true>(acc);
-          out[2 * o + 1] = acc_to_frag<1, true>(acc);
-          stream_store(dump.at(kSaveH + 16 * S + 2 * o), frag_to_bits(out[2 * o]));
-          stream_store(dump.at(kSaveH + 16 * S + 2 * o + 1), frag_to_bits(out[2 * o + 1]));
-          mask_bits[o >> 1] |= relu_bits(out[2 * o], out[2 * o + 1]) << (16 * (o & 1));
-        });
-    *reinterpret_cast<uint4*>(save + dump_off(kSaveMask + S, tile, n_tiles, kSaveTileSlots) + lane * 16) =
-        make_uint4(mask_bits[0], mask_bits[1], mask_bits[2], mask_bits[3]);
+    trunk_layer<S, true>(ring, h, xe, in, [&](auto o_, const f32x16& acc) {
+      constexpr int o = decltype(o_)::value;
+      out[2 * o] = acc_to_frag<0, true>(acc);
+      out[2 * o + 1] = acc_to_frag<1, true>(acc);
+      stream_store(dump.at(kSaveH + 16 * S + 2 * o), frag_to_bits(out[2 * o]));
+      stream_store(dump.at(kSaveH + 16 * S + 2 * o + 1), frag_to_bits(out[2 * o + 1]));
+      mask_bits[o >> 1] |= relu_bits(out[2 * o], out[2 * o + 1]) << (16 * (o & 1));
+    });
+    *mask_at(save, kSaveMask + S, tile, n_tiles, kSaveTileSlots, lane) = make_uint4(mask_bits[0], mask_bits[1], mask_bits[2], mask_bits[3]);
     mask_bits[0] = mask_bits[1] = mask_bits[2] = mask_bits[3] = 0u;
   };
   hidden(std::integral_constant<int, 0>{}, a1, a0);
@@ -135,28 +97,7 @@ __global__ __launch_bounds__(kThreads) void refnerf_trunk_fwd_kernel(
       [&](auto k_) -> bf16x8 { return a1[decltype(k_)::value]; },
       [&](auto o_, const f32x16& acc) {
         constexpr int o = decltype(o_)::value;
-        if (valid) {
-          float* zr = zout + m * ldz + 32 * o + 4 * h;
-#pragma unroll
-          for (int g = 0; g < 4; ++g)
-            *reinterpret_cast<float4*>(zr + 8 * g) = make_float4(acc[4 * g], acc[4 * g + 1], acc[4 * g + 2], acc[4 * g + 3]);
-        }
-      });
-}
-
-// One hidden step of an input-gradient chain: out = relu'(h_{l-1}) * (W_l^T in), dumped as dy_{l-1} / c_{l-1}
-template <int C0, int L, class RING>
-__device__ __forceinline__ void hidden_back(RING& ring, bf16x8 (&in)[16], bf16x8 (&out)[16], const uint4& mk,
-                                            const DumpAddr& gd) {
-  chain_layer<C0, 16, 8>(
-      ring, [&](auto) { return zero_acc(); }, [&](auto k_) -> bf16x8 { return in[decltype(k_)::value]; },
-      [&](auto o_, const f32x16& acc) {
-        constexpr int o = decltype(o_)::value;
-        const unsigned mb = mask_word(mk, o);
-        out[2 * o] = masked_frag<0>(acc, mb, 16 * (o & 1));
-        out[2 * o + 1] = masked_frag<1>(acc, mb, 16 * (o & 1));
-        stream_store(gd.at(grad_dy_slot(L - 1) + 2 * o), frag_to_bits(out[2 * o]));
-        stream_store(gd.at(grad_dy_slot(L - 1) + 2 * o + 1), frag_to_bits(out[2 * o + 1]));
+        if (valid) store_tile_row(zout + m * ldz + 32 * o, h, acc);
       });
 }
 
@@ -199,13 +140,7 @@ __device__ __forceinline__ void emb_bwd_tile(const f32x16& acc, const float (&px
 __global__ __launch_bounds__(kThreads) void refnerf_normal_kernel(
     const char* __restrict__ packed, const char* __restrict__ save, const float* __restrict__ xin_g, int64_t M,
     int64_t n_tiles, char* __restrict__ cdump, float* __restrict__ nraw) {
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int c = lane & 31, h = lane >> 5;
-  const int64_t tile = (int64_t)blockIdx.x * kWaves + wave;
-  const int64_t m = tile * kTileCols + c;
-  const bool valid = m < M;
+  const auto [lane, wave, c, h, tile, m, valid] = tile_ctx<kWaves>(M);
   float px[3] = {0, 0, 0};
   if (valid) {
 #pragma unroll
@@ -276,12 +211,7 @@ __global__ __launch_bounds__(kThreads) void refnerf_normal_kernel(
 // seed of the layer-stationary trunk backward: dy_8 = bf16(d L / d spatial_out) as the 16 fragments of the dump's dy8 slots
 __global__ __launch_bounds__(kThreads) void refnerf_dy8_kernel(const float* __restrict__ g_z, int64_t ldg, int64_t M,
                                                                int64_t n_tiles, char* __restrict__ gdump) {
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int c = lane & 31, h = lane >> 5;
-  const int64_t tile = (int64_t)blockIdx.x * kWaves + wave;
-  const int64_t m = tile * kTileCols + c;
-  const bool valid = m < M;
+  const auto [lane, wave, c, h, tile, m, valid] = tile_ctx<kWaves>(M);
   DumpAddr gd{gdump, n_tiles, tile, c, h, kGradTileSlots};
   static_for<16>([&](auto ks_) {
     constexpr int ks = decltype(ks_)::value;
@@ -305,13 +235,7 @@ __global__ __launch_bounds__(kThreads) void refnerf_dy8_kernel(const float* __re
 __global__ __launch_bounds__(kThreads) void refnerf_tangent_kernel(
     const char* __restrict__ packed, const char* __restrict__ save, const float* __restrict__ xin_g,
     const float* __restrict__ u_g, int64_t M, int64_t n_tiles, char* __restrict__ tdump) {
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int c = lane & 31, h = lane >> 5;
-  const int64_t tile = (int64_t)blockIdx.x * kWaves + wave;
-  const int64_t m = tile * kTileCols + c;
-  const bool valid = m < M;
+  const auto [lane, wave, c, h, tile, m, valid] = tile_ctx<kWaves>(M);
   float px[3] = {0, 0, 0}, pu[3] = {0, 0, 0};
   if (valid) {
 #pragma unroll
@@ -356,22 +280,9 @@ __global__ __launch_bounds__(kThreads) void refnerf_tangent_kernel(
   bf16x8 a0[16], a1[16];
   auto hidden = [&](auto s_, bf16x8(&in)[16], bf16x8(&out)[16]) {
     constexpr int S = decltype(s_)::value;
-    chain_layer<fwd_cons_base(S), fwd_nk(S), fwd_no(S)>(
-        ring, [&](auto) { return zero_acc(); },
-        [&](auto k_) -> bf16x8 {
-          constexpr int ks = decltype(k_)::value;
-          if constexpr (S == 0) return xe[ks];
-          else if constexpr (ks < 16) return in[ks];
-          else return xe[ks - 16];
-        },
-        [&](auto o_, const f32x16& acc) {
-          constexpr int o = decltype(o_)::value;
-          const unsigned mb = mask_word(mask[S], o);
-          out[2 * o] = masked_frag<0>(acc, mb, 16 * (o & 1));
-          out[2 * o + 1] = masked_frag<1>(acc, mb, 16 * (o & 1));
-          stream_store(td.at(kSaveH + 16 * S + 2 * o), frag_to_bits(out[2 * o]));
-          stream_store(td.at(kSaveH + 16 * S + 2 * o + 1), frag_to_bits(out[2 * o + 1]));
-        });
+    trunk_layer<S, false>(ring, h, xe, in, [&](auto o_, const f32x16& acc) {
+      masked_out_tile<decltype(o_)::value>(acc, mask[S], out, td, kSaveH + 16 * S);
+    });
   };
   hidden(std::integral_constant<int, 0>{}, a1, a0);
   hidden(std::integral_constant<int, 1>{}, a0, a1);
@@ -402,18 +313,8 @@ struct DirBwdSeq {
 __global__ __launch_bounds__(kThreads) void refnerf_dir_fwd_kernel(
     const char* __restrict__ packed, const float* __restrict__ dir_in, int64_t ld, int64_t M, int64_t n_tiles,
     char* __restrict__ dsave, float* __restrict__ dir_out) {
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int c = lane & 31, h = lane >> 5;
-  const int64_t tile = (int64_t)blockIdx.x * kWaves + wave;
-  const int64_t m = tile * kTileCols + c;
-  const bool valid = m < M;
-  {
-    const float* bias_g = reinterpret_cast<const float*>(packed + kRefPackDirBiasOff);
-    float* bias_l = reinterpret_cast<float*>(&smem[kBiasLdsOff]);
-    for (int i = tid; i < kDirBiasFloats; i += kThreads) bias_l[i] = bias_g[i];
-  }
+  const auto [lane, wave, c, h, tile, m, valid] = tile_ctx<kWaves>(M);
+  stage_bias<kThreads>(packed + kRefPackDirBiasOff, kDirBiasFloats);
   // input fragments: k slot (ks, h, j) <-> feature 16 ks + 8 (j >> 2) + 4 h + (j & 3); features >= 273 are zero
   bf16x8 xin[18];
   static_for<18>([&](auto ks_) {
@@ -452,8 +353,7 @@ __global__ __launch_bounds__(kThreads) void refnerf_dir_fwd_kernel(
         stream_store(dump.at(kDirSaveH + 2 * o + 1), frag_to_bits(hcol[2 * o + 1]));
         mask_bits[o >> 1] |= relu_bits(hcol[2 * o], hcol[2 * o + 1]) << (16 * (o & 1));
       });
-  *reinterpret_cast<uint4*>(dsave + dump_off(kDirSaveMask, tile, n_tiles, kDirSaveTileSlots) + lane * 16) =
-      make_uint4(mask_bits[0], mask_bits[1], 0u, 0u);
+  *mask_at(dsave, kDirSaveMask, tile, n_tiles, kDirSaveTileSlots, lane) = make_uint4(mask_bits[0], mask_bits[1], 0u, 0u);
   chain_layer<72, 8, 1>(
       ring, [&](auto) { return bias_acc(128, h); }, [&](auto k_) -> bf16x8 { return hcol[decltype(k_)::value]; },
       [&](auto, const f32x16& acc) {
@@ -469,20 +369,14 @@ __global__ __launch_bounds__(kThreads) void refnerf_dir_fwd_kernel(
 __global__ __launch_bounds__(kThreads) void refnerf_dir_bwd_kernel(
     const char* __restrict__ packed, const char* __restrict__ dsave, const float* __restrict__ g_do, int64_t M,
     int64_t n_tiles, char* __restrict__ gdump, float* __restrict__ g_dir_in, int64_t ld) {
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int c = lane & 31, h = lane >> 5;
-  const int64_t tile = (int64_t)blockIdx.x * kWaves + wave;
-  const int64_t m = tile * kTileCols + c;
-  const bool valid = m < M;
+  const auto [lane, wave, c, h, tile, m, valid] = tile_ctx<kWaves>(M);
   bf16x8 dy10 = zero_frag();
   if (valid && h == 0) {
     dy10[0] = (__bf16)g_do[m * 3 + 0];
     dy10[1] = (__bf16)g_do[m * 3 + 1];
     dy10[2] = (__bf16)g_do[m * 3 + 2];
   }
-  const uint4 mk = *reinterpret_cast<const uint4*>(dsave + dump_off(kDirSaveMask, tile, n_tiles, kDirSaveTileSlots) + lane * 16);
+  const uint4 mk = *mask_at(dsave, kDirSaveMask, tile, n_tiles, kDirSaveTileSlots, lane);
   __syncthreads();
   Ring<kDirBwdFrags / kStageFrags, DirBwdSeq> ring;
   ring.stream = packed + kRefPackDirBwdOff;
@@ -497,7 +391,7 @@ __global__ __launch_bounds__(kThreads) void refnerf_dir_bwd_kernel(
       ring, [&](auto) { return zero_acc(); }, [&](auto) -> bf16x8 { return dy10; },
       [&](auto o_, const f32x16& acc) {
         constexpr int o = decltype(o_)::value;
-        const unsigned mb = (o >> 1) == 0 ? mk.x : mk.y;
+        const unsigned mb = mask_word(mk, o);
         dy9[2 * o] = masked_frag<0>(acc, mb, 16 * (o & 1));
         dy9[2 * o + 1] = masked_frag<1>(acc, mb, 16 * (o & 1));
         stream_store(gd.at(kDirGradDy9 + 2 * o), frag_to_bits(dy9[2 * o]));
@@ -530,15 +424,6 @@ __global__ __launch_bounds__(kThreads) void refnerf_dir_bwd_kernel(
 // Blob (lnrf_refnerf_render_pack): [hi, lo] pairs of the forward stream of Dense_0..8 | fp32 biases | pairs of the
 // normal-pass stream | pairs of the directional forward stream | its fp32 biases.
 // ---------------------------------------------------------------------------------------------
-constexpr int kRef3FwdFrags = fwd3_base(9);
-constexpr int64_t kRef3FwdOff = 0;
-constexpr int64_t kRef3BiasOff = (int64_t)kRef3FwdFrags * kFragBytes;
-constexpr int64_t kRef3NrmOff = kRef3BiasOff + round_up(kBiasFloats * 4, 1024);
-constexpr int64_t kRef3DirOff = kRef3NrmOff + 2 * (int64_t)kNrmFrags * kFragBytes;
-constexpr int64_t kRef3DirBiasOff = kRef3DirOff + 2 * (int64_t)kDirFwdFrags * kFragBytes;
-constexpr int64_t kRef3Bytes = kRef3DirBiasOff + 1024;
-static_assert(kRef3FwdFrags % kStageFrags == 0 && (2 * kNrmFrags) % kStageFrags == 0 && (2 * kDirFwdFrags) % kStageFrags == 0,
-              "split streams are whole stages");
 struct RefFwd3Seq {
   static constexpr int count = 2 * fwd_cons_base(9);
   static constexpr int at(int c) { return fwd3_seq(c); }
@@ -565,18 +450,8 @@ __device__ __forceinline__ void masked_frag_split(const f32x16& acc, unsigned bi
 __global__ __launch_bounds__(kSplitThreads) void refnerf_render_split_kernel(
     const char* __restrict__ packed3, const float* __restrict__ xin_g, int64_t M, float* __restrict__ zout, int64_t ldz,
     float* __restrict__ nraw, uint4* __restrict__ mask_buf) {
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int c = lane & 31, h = lane >> 5;
-  const int64_t tile = (int64_t)blockIdx.x * kSplitWaves + wave;
-  const int64_t m = tile * kTileCols + c;
-  const bool valid = m < M;
-  {
-    const float* bias_g = reinterpret_cast<const float*>(packed3 + kRef3BiasOff);
-    float* bias_l = reinterpret_cast<float*>(&smem[kBiasLdsOff]);
-    for (int i = tid; i < kBiasFloats; i += kSplitThreads) bias_l[i] = bias_g[i];
-  }
+  const auto [lane, wave, c, h, tile, m, valid] = tile_ctx<kSplitWaves>(M);
+  stage_bias<kSplitThreads>(packed3 + kRef3BiasOff, kBiasFloats);
   float px[3] = {0, 0, 0};
   if (valid) {
 #pragma unroll
@@ -595,45 +470,16 @@ __global__ __launch_bounds__(kSplitThreads) void refnerf_render_split_kernel(
     ring.lane = lane;
     ring.prologue();
     bf16x8 xe_hi[4], xe_lo[4];
-    static_for<4>([&](auto ks_) {
-      constexpr int ks = decltype(ks_)::value;
-#pragma unroll
-      for (int pp = 0; pp < 4; ++pp) {
-        const int p = 4 * ks + pp;
-        float sn = 0.0f, co = 0.0f;
-        if (p < 15) {
-          const int pg = 15 * h + p;
-          const int cd = pg / 10, f = pg - 10 * cd;
-          const float v = cd == 0 ? px[0] : (cd == 1 ? px[1] : px[2]);
-          sincos_pe(v * (float)(1 << f), &sn, &co);
-        }
-        split_store(sn, xe_hi[ks], xe_lo[ks], 2 * pp);
-        split_store(co, xe_hi[ks], xe_lo[ks], 2 * pp + 1);
-      }
-    });
+    x_encode(px, h, [&](auto ks_, int j, float v) { split_store(v, xe_hi[decltype(ks_)::value], xe_lo[decltype(ks_)::value], j); });
     auto hidden = [&](auto s_, bf16x8(&inh)[16], bf16x8(&inl)[16], bf16x8(&outh)[16], bf16x8(&outl)[16]) {
       constexpr int S = decltype(s_)::value;
       unsigned mb[4] = {0u, 0u, 0u, 0u};
-      chain_layer_split<fwd_cons_base(S), fwd_nk(S), fwd_no(S)>(
-          ring, [&](auto o_) { return bias_acc(fwd_bias_base(S) + 32 * decltype(o_)::value, h); },
-          [&](auto k_) -> bf16x8 {
-            constexpr int ks = decltype(k_)::value;
-            if constexpr (S == 0) return xe_hi[ks];
-            else if constexpr (ks < 16) return inh[ks];
-            else return xe_hi[ks - 16];
-          },
-          [&](auto k_) -> bf16x8 {
-            constexpr int ks = decltype(k_)::value;
-            if constexpr (S == 0) return xe_lo[ks];
-            else if constexpr (ks < 16) return inl[ks];
-            else return xe_lo[ks - 16];
-          },
-          [&](auto o_, const f32x16& acc) {
-            constexpr int o = decltype(o_)::value;
-            acc_to_frag_split<0, true>(acc, outh[2 * o], outl[2 * o]);
-            acc_to_frag_split<1, true>(acc, outh[2 * o + 1], outl[2 * o + 1]);
-            mb[o >> 1] |= acc_positive_bits(acc) << (16 * (o & 1));
-          });
+      trunk_layer_split<S>(ring, h, xe_hi, xe_lo, inh, inl, [&](auto o_, const f32x16& acc) {
+        constexpr int o = decltype(o_)::value;
+        acc_to_frag_split<0, true>(acc, outh[2 * o], outl[2 * o]);
+        acc_to_frag_split<1, true>(acc, outh[2 * o + 1], outl[2 * o + 1]);
+        mb[o >> 1] |= acc_positive_bits(acc) << (16 * (o & 1));
+      });
       my_masks[S * 64] = make_uint4(mb[0], mb[1], mb[2], mb[3]);
     };
     hidden(std::integral_constant<int, 0>{}, a1h, a1l, a0h, a0l);
@@ -651,12 +497,7 @@ __global__ __launch_bounds__(kSplitThreads) void refnerf_render_split_kernel(
         [&](auto k_) -> bf16x8 { return a1l[decltype(k_)::value]; },
         [&](auto o_, const f32x16& acc) {
           constexpr int o = decltype(o_)::value;
-          if (valid) {
-            float* zr = zout + m * ldz + 32 * o + 4 * h;
-#pragma unroll
-            for (int g = 0; g < 4; ++g)
-              *reinterpret_cast<float4*>(zr + 8 * g) = make_float4(acc[4 * g], acc[4 * g + 1], acc[4 * g + 2], acc[4 * g + 3]);
-          }
+          if (valid) store_tile_row(zout + m * ldz + 32 * o, h, acc);
         });
   }
   __syncthreads();  // every wave is done with the forward stream's ring slots
@@ -700,8 +541,6 @@ __global__ __launch_bounds__(kSplitThreads) void refnerf_render_split_kernel(
             emb_bwd_tile<decltype(o_)::value>(acc, pl, h, nr);
           });
     };
-    using I = std::integral_constant<int, 0>;
-    (void)sizeof(I);
     back(std::integral_constant<int, 0>{}, std::integral_constant<int, 8>{}, a1h, a1l, a0h, a0l);  // c_7
     back(std::integral_constant<int, 1>{}, std::integral_constant<int, 7>{}, a0h, a0l, a1h, a1l);  // c_6
     back(std::integral_constant<int, 2>{}, std::integral_constant<int, 6>{}, a1h, a1l, a0h, a0l);  // c_5
@@ -724,18 +563,8 @@ __global__ __launch_bounds__(kSplitThreads) void refnerf_render_split_kernel(
 
 __global__ __launch_bounds__(kSplitThreads) void refnerf_dir_fwd_split_kernel(
     const char* __restrict__ packed3, const float* __restrict__ dir_in, int64_t ld, int64_t M, float* __restrict__ dir_out) {
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int c = lane & 31, h = lane >> 5;
-  const int64_t tile = (int64_t)blockIdx.x * kSplitWaves + wave;
-  const int64_t m = tile * kTileCols + c;
-  const bool valid = m < M;
-  {
-    const float* bias_g = reinterpret_cast<const float*>(packed3 + kRef3DirBiasOff);
-    float* bias_l = reinterpret_cast<float*>(&smem[kBiasLdsOff]);
-    for (int i = tid; i < kDirBiasFloats; i += kSplitThreads) bias_l[i] = bias_g[i];
-  }
+  const auto [lane, wave, c, h, tile, m, valid] = tile_ctx<kSplitWaves>(M);
+  stage_bias<kSplitThreads>(packed3 + kRef3DirBiasOff, kDirBiasFloats);
   bf16x8 xh[18], xl[18];
   static_for<18>([&](auto ks_) {
     constexpr int ks = decltype(ks_)::value;
@@ -780,121 +609,65 @@ __global__ __launch_bounds__(kSplitThreads) void refnerf_dir_fwd_split_kernel(
       });
 }
 
+// element e of a stream of [hi, lo] fragment pairs: (fragment of the plain stream, lane, j, which half)
+struct SplitElem {
+  int g, lane, j;
+  bool lo_part;
+  __device__ explicit SplitElem(int64_t e) : g((int)(e >> 10)), lane((int)((e >> 3) & 63)), j((int)(e & 7)), lo_part((e >> 9) & 1) {}
+};
 __global__ void refnerf_render_pack_kernel(const float* __restrict__ params, char* __restrict__ packed3) {
   const int64_t n_f = (int64_t)kRef3FwdFrags * 512, n_n = 2 * (int64_t)kNrmFrags * 512, n_d = 2 * (int64_t)kDirFwdFrags * 512;
   const int64_t total = n_f + kBiasFloats + n_n + n_d + kDirBiasFloats;
   for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (int64_t)gridDim.x * blockDim.x) {
-    int idx = -1;
-    bool lo_part = false;
-    __bf16* dst = nullptr;
-    if (e < n_f) {  // pairs of the forward stream of Dense_0..8 (layout: nerf_layout.h fwd3_base)
-      const int g = (int)(e >> 9), lane = (int)((e >> 3) & 63), j = (int)(e & 7);
-      int s = 0;
-      for (int i = 1; i < 9; ++i)
-        if (g >= fwd3_base(i)) s = i;
-      const int loc = g - fwd3_base(s);
-      if (loc < 2 * fwd_nk(s) * fwd_no(s)) idx = fwd_weight_index(s, (loc >> 1) / fwd_nk(s), (loc >> 1) % fwd_nk(s), lane, j);
-      lo_part = loc & 1;
-      dst = reinterpret_cast<__bf16*>(packed3 + kRef3FwdOff) + e;
-    } else if (e < n_f + kBiasFloats) {
-      const int i = (int)(e - n_f);
-      int s = 0;
-      for (int k = 1; k < kFwdLayers; ++k)
-        if (i >= fwd_bias_base(k)) s = k;
-      const int bi = s <= 8 ? fwd_bias_index(s, i - fwd_bias_base(s)) : -1;
-      reinterpret_cast<float*>(packed3 + kRef3BiasOff)[i] = bi >= 0 ? params[bi] : 0.0f;
-      continue;
-    } else if (e < n_f + kBiasFloats + n_n) {
-      const int64_t ee = e - n_f - kBiasFloats;
-      const int gg = (int)(ee >> 9), lane = (int)((ee >> 3) & 63), j = (int)(ee & 7);
-      const int g = gg >> 1;
-      int u = 0;
-      for (int i = 1; i < kNrmLayers; ++i)
-        if (g >= nrm_base(i)) u = i;
-      const int loc = g - nrm_base(u);
-      idx = nrm_weight_index(u, loc / nrm_nk(u), loc % nrm_nk(u), lane, j);
-      lo_part = gg & 1;
-      dst = reinterpret_cast<__bf16*>(packed3 + kRef3NrmOff) + ee;
-    } else if (e < n_f + kBiasFloats + n_n + n_d) {
-      const int64_t ee = e - n_f - kBiasFloats - n_n;
-      const int gg = (int)(ee >> 9), lane = (int)((ee >> 3) & 63), j = (int)(ee & 7);
-      idx = dir_fwd_weight_index(gg >> 1, lane, j);
-      lo_part = gg & 1;
-      dst = reinterpret_cast<__bf16*>(packed3 + kRef3DirOff) + ee;
+    int64_t ee = e;
+    if (ee < n_f) {  // pairs of the forward stream of Dense_0..8 (layout: nerf_layout.h fwd3_base)
+      const SplitElem q(ee);
+      reinterpret_cast<__bf16*>(packed3 + kRef3FwdOff)[ee] =
+          split_half(param_or_zero(params, fwd3_stream_index((int)(ee >> 9), q.lane, q.j, true)), q.lo_part);
+    } else if ((ee -= n_f) < kBiasFloats) {
+      reinterpret_cast<float*>(packed3 + kRef3BiasOff)[ee] = param_or_zero(params, bias_block_index((int)ee, true));
+    } else if ((ee -= kBiasFloats) < n_n) {
+      const SplitElem q(ee);
+      reinterpret_cast<__bf16*>(packed3 + kRef3NrmOff)[ee] = split_half(param_or_zero(params, nrm_stream_index(q.g, q.lane, q.j)), q.lo_part);
+    } else if ((ee -= n_n) < n_d) {
+      const SplitElem q(ee);
+      reinterpret_cast<__bf16*>(packed3 + kRef3DirOff)[ee] = split_half(param_or_zero(params, dir_fwd_weight_index(q.g, q.lane, q.j)), q.lo_part);
     } else {
-      const int i = (int)(e - n_f - kBiasFloats - n_n - n_d);
-      const int bi = dir_bias_index(i);
-      reinterpret_cast<float*>(packed3 + kRef3DirBiasOff)[i] = bi >= 0 ? params[bi] : 0.0f;
-      continue;
+      ee -= n_d;
+      reinterpret_cast<float*>(packed3 + kRef3DirBiasOff)[ee] = param_or_zero(params, dir_bias_index((int)ee));
     }
-    const float w = idx >= 0 ? params[idx] : 0.0f;
-    const __bf16 hi = (__bf16)w;
-    *dst = lo_part ? (__bf16)(w - (float)hi) : hi;
   }
 }
 
 // ---------------------------------------------------------------------------------------------
-// packing: the NeRFModel streams restricted to the trunk (head fragments zero) + the normal-pass stream
+// packing: the NeRFModel streams restricted to the trunk (head fragments zero), the normal-pass stream, the directional
+// block.  Regions in blob order: (byte offset, elements, bf16 fragments or fp32 biases).
 // ---------------------------------------------------------------------------------------------
 __global__ void refnerf_pack_kernel(const float* __restrict__ params, char* __restrict__ packed) {
-  const int64_t total_f = (int64_t)kFwdFrags * 512;
-  const int64_t total_b = (int64_t)kBwdFrags * 512;
-  const int64_t total_n = (int64_t)kNrmFrags * 512;
-  const int64_t total_d = (int64_t)(kDirFwdFrags + kDirBwdFrags) * 512;
-  const int64_t total = total_f + total_b + kBiasFloats + total_n + total_d + kDirBiasFloats;
+  const int64_t total_f = (int64_t)kFwdFrags * 512, total_b = (int64_t)kBwdFrags * 512, total_n = (int64_t)kNrmFrags * 512;
+  const int64_t total_df = (int64_t)kDirFwdFrags * 512, total_db = (int64_t)kDirBwdFrags * 512;
+  const int64_t total = total_f + total_b + kBiasFloats + total_n + total_df + total_db + kDirBiasFloats;
   for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total;
        e += (int64_t)gridDim.x * blockDim.x) {
-    if (e < total_f + total_b) {
-      const bool fwd = e < total_f;
-      const int64_t ee = fwd ? e : e - total_f;
-      const int g = (int)(ee >> 9), lane = (int)((ee >> 3) & 63), j = (int)(ee & 7);
-      int idx = -1;
-      if (fwd) {
-        int s = 0;
-        for (int i = 1; i < kFwdLayers; ++i)
-          if (g >= fwd_base(i)) s = i;
-        const int loc = g - fwd_base(s);
-        if (s <= 8 && loc < fwd_nk(s) * fwd_no(s)) idx = fwd_weight_index(s, loc / fwd_nk(s), loc % fwd_nk(s), lane, j);
-      } else {
-        int t = 0;
-        for (int i = 1; i < kBwdLayers; ++i)
-          if (g >= bwd_base(i)) t = i;
-        const int loc = g - bwd_base(t);
-        if (t >= 2 && loc < bwd_nk(t) * bwd_no(t)) idx = bwd_weight_index(t, loc / bwd_nk(t), loc % bwd_nk(t), lane, j);
+    int64_t ee = e;
+    int region = 0;  // 0 forward, 1 transposed, 2 bias, 3 normal pass, 4 / 5 directional forward / transposed, 6 its bias
+    const int64_t sizes[6] = {total_f, total_b, kBiasFloats, total_n, total_df, total_db};
+#pragma unroll
+    for (int r = 0; r < 6; ++r)
+      if (region == r && ee >= sizes[r]) {
+        ee -= sizes[r];
+        ++region;
       }
-      const float v = idx >= 0 ? params[idx] : 0.0f;
-      reinterpret_cast<__bf16*>(packed + (fwd ? kPackFwdOff : kPackBwdOff))[ee] = (__bf16)v;
-    } else if (e < total_f + total_b + kBiasFloats) {
-      const int i = (int)(e - total_f - total_b);
-      int s = 0;
-      for (int k = 1; k < kFwdLayers; ++k)
-        if (i >= fwd_bias_base(k)) s = k;
-      const int idx = s <= 8 ? fwd_bias_index(s, i - fwd_bias_base(s)) : -1;
-      reinterpret_cast<float*>(packed + kPackBiasOff)[i] = idx >= 0 ? params[idx] : 0.0f;
-    } else if (e >= total_f + total_b + kBiasFloats + total_n) {  // directional block
-      const int64_t ee = e - (total_f + total_b + kBiasFloats + total_n);
-      if (ee < total_d) {
-        const bool fwd = ee < (int64_t)kDirFwdFrags * 512;
-        const int64_t e2 = fwd ? ee : ee - (int64_t)kDirFwdFrags * 512;
-        const int g = (int)(e2 >> 9), lane = (int)((e2 >> 3) & 63), j = (int)(e2 & 7);
-        const int idx = fwd ? dir_fwd_weight_index(g, lane, j) : dir_bwd_weight_index(g, lane, j);
-        reinterpret_cast<__bf16*>(packed + (fwd ? kRefPackDirFwdOff : kRefPackDirBwdOff))[e2] =
-            (__bf16)(idx >= 0 ? params[idx] : 0.0f);
-      } else {
-        const int i = (int)(ee - total_d);
-        const int idx = dir_bias_index(i);
-        reinterpret_cast<float*>(packed + kRefPackDirBiasOff)[i] = idx >= 0 ? params[idx] : 0.0f;
-      }
-    } else {
-      const int64_t ee = e - total_f - total_b - kBiasFloats;
-      const int g = (int)(ee >> 9), lane = (int)((ee >> 3) & 63), j = (int)(ee & 7);
-      int u = 0;
-      for (int i = 1; i < kNrmLayers; ++i)
-        if (g >= nrm_base(i)) u = i;
-      const int loc = g - nrm_base(u);
-      const int idx = nrm_weight_index(u, loc / nrm_nk(u), loc % nrm_nk(u), lane, j);
-      reinterpret_cast<__bf16*>(packed + kRefPackNrmOff)[ee] = (__bf16)(idx >= 0 ? params[idx] : 0.0f);
-    }
+    const int g = (int)(ee >> 9), lane = (int)((ee >> 3) & 63), j = (int)(ee & 7);
+    const int64_t offs[7] = {kPackFwdOff, kPackBwdOff, kPackBiasOff, kRefPackNrmOff, kRefPackDirFwdOff, kRefPackDirBwdOff,
+                             kRefPackDirBiasOff};
+    const int idx = region == 0 ? fwd_stream_index(g, lane, j, true) : region == 1 ? bwd_stream_index(g, lane, j, true)
+                  : region == 2 ? bias_block_index((int)ee, true) : region == 3 ? nrm_stream_index(g, lane, j)
+                  : region == 4 ? dir_fwd_weight_index(g, lane, j) : region == 5 ? dir_bwd_weight_index(g, lane, j)
+                                                                                  : dir_bias_index((int)ee);
+    const float v = param_or_zero(params, idx);
+    if (region == 2 || region == 6) reinterpret_cast<float*>(packed + offs[region])[ee] = v;
+    else reinterpret_cast<__bf16*>(packed + offs[region])[ee] = (__bf16)v;
   }
 }
 

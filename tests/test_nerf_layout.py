@@ -311,3 +311,61 @@ def test_every_gradient_entry_has_exactly_one_owner(H, which, n_tiles):
     missing, twice, stray = (counts == 0) & (want == 1), counts > 1, (counts > 0) & (want == 0)
     assert not missing.any() and not twice.any() and not stray.any(), (
         f"{which}: {missing.sum()} unowned, {twice.sum()} owned more than once, {stray.sum()} outside the caller's entries")
+
+
+STREAMS = {"fwd": 0, "bwd": 1, "fwd3": 2, "bias": 3, "nrm": 4, "dir_fwd": 5, "dir_bwd": 6, "dir_bias": 7}
+
+
+def stream_indices(H, stream, ref=False):
+    """The index array of a whole stream through the pack walks of nerf_layout.h (what the pack kernels call)."""
+    H.lnrf_host_stream_indices.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_void_p]
+    H.lnrf_host_stream_indices.restype = ctypes.c_int64
+    n = H.lnrf_host_stream_indices(STREAMS[stream], int(ref), None)
+    assert n > 0
+    out = np.full(n, -2, np.int32)
+    assert H.lnrf_host_stream_indices(STREAMS[stream], int(ref), out.ctypes.data) == n
+    return out
+
+
+def test_stream_index_arrays_are_the_per_element_exports(H):
+    fwd, bwd, bias = stream_indices(H, "fwd"), stream_indices(H, "bwd"), stream_indices(H, "bias")
+    assert fwd.shape == (1200 * 512,) and bwd.shape == (1120 * 512,) and bias.shape == (2496,)
+    rng = np.random.default_rng(0)
+    for e in rng.integers(0, fwd.size, 2000):
+        assert fwd[e] == H.lnrf_host_fwd_weight_index(int(e >> 9), int((e >> 3) & 63), int(e & 7))
+    for e in rng.integers(0, bwd.size, 2000):
+        assert bwd[e] == H.lnrf_host_bwd_weight_index(int(e >> 9), int((e >> 3) & 63), int(e & 7))
+    assert all(bias[i] == H.lnrf_host_fwd_bias_index(i) for i in range(2496))
+
+
+def test_split_stream_mirrors_the_forward_stream(H):
+    """Fragments 2p (hi) and 2p + 1 (lo) of a layer of the split stream both carry the indices of forward fragment p of that
+    layer; the stage-alignment padding of either stream is -1."""
+    fwd = stream_indices(H, "fwd").reshape(1200, 512)
+    fwd3 = stream_indices(H, "fwd3").reshape(2384, 512)
+    covered = np.zeros(2384, bool)
+    for s in range(11):
+        nk, no, base = (H.lnrf_host_fwd_layer_info(s, w) for w in range(3))
+        base3 = H.lnrf_host_fwd3_base(s)
+        for p in range(nk * no):
+            assert (fwd3[base3 + 2 * p] == fwd[base + p]).all() and (fwd3[base3 + 2 * p + 1] == fwd[base + p]).all()
+            covered[base3 + 2 * p:base3 + 2 * p + 2] = True
+        end = H.lnrf_host_fwd_layer_info(s + 1, 2) if s < 10 else 1200
+        assert (fwd[base + nk * no:end] == -1).all()
+    assert (fwd3[~covered] == -1).all() and (~covered).sum() == 2384 - 2 * 1186
+
+
+def test_ref_nerf_restriction_keeps_the_trunk_and_zeroes_the_rest(H):
+    """RefNERFModel's blobs: forward stream layers <= 8, transposed stream layers >= 2 (Dense_8..1^T) and their biases as in
+    the unrestricted maps, -1 everywhere else."""
+    fwd_end = H.lnrf_host_fwd_layer_info(9, 2) * 512    # first element of stream layer 9
+    bwd_start = H.lnrf_host_bwd_layer_info(2, 2) * 512   # first element of transposed layer 2
+    bias_end = H.lnrf_host_fwd_layer_info(9, 3)
+    fwd3_end = H.lnrf_host_fwd3_base(9) * 512
+    for stream, lo, hi in [("fwd", 0, fwd_end), ("bwd", bwd_start, 1120 * 512), ("bias", 0, bias_end), ("fwd3", 0, fwd3_end)]:
+        full, ref = stream_indices(H, stream), stream_indices(H, stream, ref=True)
+        assert 0 <= lo < hi <= full.size
+        assert (ref[lo:hi] == full[lo:hi]).all(), stream
+        assert (ref[:lo] == -1).all() and (ref[hi:] == -1).all(), stream
+        assert (full[:lo] >= 0).any() or lo == 0
+        assert (full[hi:] >= 0).any() or hi == full.size
