@@ -548,6 +548,35 @@ int lnrf_mc_emit(const float* vol, int64_t nx, int64_t ny, int64_t nz, float lev
 /* (host) the compile-time case table: out[256 * 16] int8, triangles as triples of edge numbers, -1 terminated. */
 int lnrf_mc_case_table(int8_t* out);
 
+/* ----------------------------------------------------------- point cloud ---- */
+
+/* Exact neighbour search over a point cloud (the KD-tree queries of point_cloud/main.go:111-125, 177-187) on a uniform
+ * grid of cubic cells: origin lo, edge h > 0, dims [gx, gy, gz] each in [1, 4096] and at most 2^24 cells in all
+ * (LNRF_ERR_SHAPE beyond).  Results do not depend on h.  Cell, order, distance and tie conventions: the header comment
+ * of csrc/pointcloud.hip.  Point and query counts above INT32_MAX give LNRF_ERR_SHAPE.  No entry point allocates,
+ * copies, synchronises or uses atomics. */
+typedef struct lnrf_pc_grid {
+  float lo[3];
+  float h;
+  int32_t dims[3];
+  int32_t pad_;
+} lnrf_pc_grid;
+
+/* ids [n] (device int32): linear cell id (cx*gy + cy)*gz + cz of each point of pts [n, 3], clamped into the grid (a
+ * point on the upper face belongs to the last cell).  The caller sorts by it (stable) and builds cell_start. */
+int lnrf_pc_cell_ids(const lnrf_pc_grid* grid, const float* pts, int64_t n, int32_t* ids, lnrf_stream_t stream);
+/* out_d2 [m]: squared distance from each query to its k-th nearest point, 1 <= k <= 32 (LNRF_ERR_UNSUPPORTED above); a
+ * query that is one of the points counts itself; +inf when n < k.  sorted_pts [n, 3]: the points in cell order,
+ * cell_start [cells + 1] int32.  Queries should come in cell order (speed only). */
+int lnrf_pc_knn_dist2(const lnrf_pc_grid* grid, const float* sorted_pts, const int32_t* cell_start, int64_t n,
+                      const float* queries, int64_t m, int32_t k, float* out_d2, lnrf_stream_t stream);
+/* out_d2 / out_idx [m]: squared distance to the nearest point with d2 <= max_radius^2 (max_radius >= 0, may be +inf)
+ * and its original index order[j], the lowest index among equal distances; +inf and -1 without one.  Queries may lie
+ * anywhere in space. */
+int lnrf_pc_nearest(const lnrf_pc_grid* grid, const float* sorted_pts, const int32_t* order,
+                    const int32_t* cell_start, int64_t n, const float* queries, int64_t m, float max_radius,
+                    float* out_d2, int32_t* out_idx, lnrf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

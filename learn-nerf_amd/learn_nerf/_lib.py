@@ -34,6 +34,10 @@ class NgpMlpDesc(ctypes.Structure):
                 ("dense_offset", c_int64)]
 
 
+class PcGrid(ctypes.Structure):
+    _fields_ = [("lo", c_float * 3), ("h", c_float), ("dims", c_int32 * 3), ("pad_", c_int32)]
+
+
 _P = c_void_p
 _F3 = POINTER(c_float)
 
@@ -145,6 +149,9 @@ PROTOTYPES = {
     "lnrf_mc_count": (c_int32, [_P, c_int64, c_int64, c_int64, c_float, _P, _P, _P]),
     "lnrf_mc_emit": (c_int32, [_P, c_int64, c_int64, c_int64, c_float, _P, c_int64, c_int64, _P, _P, _P]),
     "lnrf_mc_case_table": (c_int32, [_P]),
+    "lnrf_pc_cell_ids": (c_int32, [POINTER(PcGrid), _P, c_int64, _P, _P]),
+    "lnrf_pc_knn_dist2": (c_int32, [POINTER(PcGrid), _P, _P, c_int64, _P, c_int64, c_int32, _P, _P]),
+    "lnrf_pc_nearest": (c_int32, [POINTER(PcGrid), _P, _P, _P, c_int64, _P, c_int64, c_float, _P, _P, _P]),
 }
 
 _lib = None
