@@ -577,6 +577,42 @@ int lnrf_pc_nearest(const lnrf_pc_grid* grid, const float* sorted_pts, const int
                     const int32_t* cell_start, int64_t n, const float* queries, int64_t m, float max_radius,
                     float* out_d2, int32_t* out_idx, lnrf_stream_t stream);
 
+/* -------------------------------------------------------------- ray casting ---- */
+
+/* Ray casting against a triangle mesh (the collider and RayCaster queries of simple_dataset/main.go:96-100, 132-136): an
+ * implicit binary tree over Morton-sorted leaves of leaf_size triangles.  The pinned fp32 ray-triangle test, the tie
+ * rule, the node layout, the per-ray margin of the box test and the domain on which it is conservative: the header
+ * comment of csrc/raycast.hip.  Results do not depend on leaf_size.  center / half: centre and half extents of the
+ * mesh's box, radius >= half[0] + half[1] + half[2], > 0; 1 <= n_tris <= 2^28, 1 <= leaf_size <= 64 (LNRF_ERR_SHAPE
+ * beyond).  No entry point allocates, copies, synchronises or uses atomics. */
+typedef struct lnrf_rt_bvh {
+  float center[3];
+  float radius;
+  float half[3];
+  int32_t n_tris;
+  int32_t leaf_size;
+  int32_t pad_;
+} lnrf_rt_bvh;
+
+/* (host) rows of the nodes array [rows, 8] fp32 for n_tris triangles: twice the power of two >= ceil(n_tris /
+ * leaf_size); -1 outside the limits above. */
+int64_t lnrf_rt_node_count(int64_t n_tris, int32_t leaf_size);
+/* codes [n_tris] (device int32): 30-bit Morton code of each centroid of tris [n_tris, 3, 3] in the box, 2^30 for a
+ * sliver (always-tested set).  The caller sorts by it (stable) and gathers the triangles. */
+int lnrf_rt_morton(const lnrf_rt_bvh* bvh, const float* tris, int32_t* codes, lnrf_stream_t stream);
+/* nodes [lnrf_rt_node_count, 8] (16-byte aligned): the bounds of every node over sorted_tris, leaves first, then level
+ * by level. */
+int lnrf_rt_fit(const lnrf_rt_bvh* bvh, const float* sorted_tris, float* nodes, lnrf_stream_t stream);
+/* out_t / out_id [m]: parameter and original index order[j] of the nearest accepted triangle of each ray of rays
+ * [m, 2, 3] (origin, direction), the lowest index among equal t; +inf and -1 without one.  window [m, 2] = (t_min,
+ * t_max) per ray, or NULL for (0, +inf). */
+int lnrf_rt_closest(const lnrf_rt_bvh* bvh, const float* sorted_tris, const int32_t* order, const float* nodes,
+                    const float* rays, const float* window, int64_t m, float* out_t, int32_t* out_id,
+                    lnrf_stream_t stream);
+/* out [m] (uint8): 1 iff any triangle is accepted within the ray's window, else 0. */
+int lnrf_rt_occluded(const lnrf_rt_bvh* bvh, const float* sorted_tris, const float* nodes, const float* rays,
+                     const float* window, int64_t m, uint8_t* out, lnrf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -38,6 +38,11 @@ class PcGrid(ctypes.Structure):
     _fields_ = [("lo", c_float * 3), ("h", c_float), ("dims", c_int32 * 3), ("pad_", c_int32)]
 
 
+class RtBvh(ctypes.Structure):
+    _fields_ = [("center", c_float * 3), ("radius", c_float), ("half", c_float * 3), ("n_tris", c_int32),
+                ("leaf_size", c_int32), ("pad_", c_int32)]
+
+
 _P = c_void_p
 _F3 = POINTER(c_float)
 
@@ -152,6 +157,11 @@ PROTOTYPES = {
     "lnrf_pc_cell_ids": (c_int32, [POINTER(PcGrid), _P, c_int64, _P, _P]),
     "lnrf_pc_knn_dist2": (c_int32, [POINTER(PcGrid), _P, _P, c_int64, _P, c_int64, c_int32, _P, _P]),
     "lnrf_pc_nearest": (c_int32, [POINTER(PcGrid), _P, _P, _P, c_int64, _P, c_int64, c_float, _P, _P, _P]),
+    "lnrf_rt_node_count": (c_int64, [c_int64, c_int32]),
+    "lnrf_rt_morton": (c_int32, [POINTER(RtBvh), _P, _P, _P]),
+    "lnrf_rt_fit": (c_int32, [POINTER(RtBvh), _P, _P, _P]),
+    "lnrf_rt_closest": (c_int32, [POINTER(RtBvh), _P, _P, _P, _P, _P, c_int64, _P, _P, _P]),
+    "lnrf_rt_occluded": (c_int32, [POINTER(RtBvh), _P, _P, _P, _P, c_int64, _P, _P]),
 }
 
 _lib = None
