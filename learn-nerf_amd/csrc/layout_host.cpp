@@ -105,6 +105,12 @@ int lnrf_host_grad_slot(int what, int arg) {
   return what == 0 ? kGradDy11 : what == 1 ? kGradDy10m : what == 2 ? grad_dy_slot(arg) : kGradSlots;
 }
 int lnrf_host_demb_feat(int ks, int h, int j) { return demb_feat(ks, h, j); }
+int lnrf_host_hidden_feat(int ks, int h, int j) { return hidden_feat(ks, h, j); }
+// what 0 bytes per fragment, 1 evaluations per tile, 2 tiles per workgroup (dumps are padded to whole workgroups)
+int lnrf_host_dump_info(int what) { return what == 0 ? kFragBytes : what == 1 ? kTileCols : kWaves; }
+// ReLU-mask slot (kSaveMask): bit of a lane's 128 that belongs to element j of fragment ks of the masked tensor, i.e. to
+// accumulator register q = 8 (ks & 1) + j of out tile o = ks >> 1: bit 16 o + q; the lane's uint4 sits at lane * 16
+int lnrf_host_mask_bit(int ks, int j) { return 16 * (ks >> 1) + 8 * (ks & 1) + j; }
 int lnrf_host_dump_lane_off(int slot, int c, int hh) { return dump_lane_off(slot, c, hh); }
 void lnrf_host_sincos_pe(float r, float* s, float* c) { lnrf::sincos_pe(r, s, c); }
 

@@ -138,8 +138,10 @@ def test_dump_lane_offsets_are_a_permutation_and_conflict_free(H):
         assert len(banks) == 64
 
 
-def test_emulated_forward_chain_matches_oracle(H):
-    """Run the forward 'program' of nerf_fwd_kernel for one 32-evaluation tile with the real packing maps."""
+def emulated_forward_chain(H):
+    """The forward 'program' of nerf_fwd_kernel for one 32-evaluation tile with the real packing maps.  -> the emulator's
+    density and rgb, the oracle's, and `tiles`: per stream layer the accumulator tiles [out tile][64 lanes][16 registers]
+    (test_nerf_dump_decode_cpu.py places them in a save buffer), plus the embedding fragments and inputs."""
     gen = torch.Generator().manual_seed(0)
     dims = OM.nerf_layer_dims()
     flat = OM.lecun_normal_init(dims, gen)
@@ -196,21 +198,30 @@ def test_emulated_forward_chain_matches_oracle(H):
             frags += [bf16(v[:, :8]).astype(np.float64), bf16(v[:, 8:]).astype(np.float64)]
         return outs, frags
 
-    _, act = layer(0, list(xin), True)
+    tiles = {}
+    tiles[0], act = layer(0, list(xin), True)
     for s in (1, 2, 3, 4):
-        _, act = layer(s, act, True)
-    _, act = layer(5, act + list(xin), True)
+        tiles[s], act = layer(s, act, True)
+    tiles[5], act = layer(5, act + list(xin), True)
     for s in (6, 7):
-        _, act = layer(s, act, True)
-    _, z = layer(8, act, False)
+        tiles[s], act = layer(s, act, True)
+    tiles[8], z = layer(8, act, False)
     outs, h10 = layer(9, z + list(din), True)
+    tiles[9] = outs
     logit = outs[4][:32, 0]  # row 0 of out-tile 4 lives in register 0 of lanes 0..31
     density = np.logaddexp(logit, 0.0)
     outs11, _ = layer(10, h10[:8], False)
     rgb = np.tanh(outs11[0][:32, :3])
     rd, rr, _ = OM.nerf_mlp(flat.double(), x.double(), d.double(), operand_round=OM.bf16_round)
-    assert np.abs(rgb - rr.numpy()).max() < 2e-5
-    assert np.abs(density - rd.numpy()[:, 0]).max() < 2e-5
+    return dict(density=density, rgb=rgb, ref_density=rd.numpy()[:, 0], ref_rgb=rr.numpy(), tiles=tiles, xin=xin, din=din,
+                x_emb=xe, d_emb=de)
+
+
+def test_emulated_forward_chain_matches_oracle(H):
+    """Run the forward 'program' of nerf_fwd_kernel for one 32-evaluation tile with the real packing maps."""
+    e = emulated_forward_chain(H)
+    assert np.abs(e["rgb"] - e["ref_rgb"]).max() < 2e-5
+    assert np.abs(e["density"] - e["ref_density"]).max() < 2e-5
 
 
 def test_slot_orders_keep_the_merged_weight_gradient_operands_adjacent(H):
