@@ -246,7 +246,14 @@ int lnrf_hashgrid_bwd_bucketed(const lnrf_hashgrid_desc* desc, const float* x, c
  * (InstantNGPRefNERFModel, instant_ngp.py:57-89: normals = -d out[:,0]/dx, ref_nerf.py:38-43):
  *   jvp:        enc_t-shaped (d enc / d x) u,            u [M,3]
  *   input_grad: g_x[M,3] = (d enc / d x)^T g_enc
- *   bwd_dir:    g_tables += d/d tables of < (d enc / d x) u , g_enc >   (second-order term) */
+ *   bwd_dir:    g_tables += d/d tables of < (d enc / d x) u , g_enc >   (second-order term)
+ * Boundary convention of all three: the derivative along an axis is zero when the point lies on or outside the
+ * bounding box on that axis (x <= bbox_min or x >= bbox_max: the clip of instant_ngp.py:138-140 has zero slope
+ * there; exactly 0.0 in input_grad, and in jvp for a u along that axis).  With smooth == 0 the encoding is only
+ * piecewise differentiable: the maps return the one-sided derivative of the cell that contains the point (the cell
+ * the forward pass interpolates in); with smooth == 1 the derivative is continuous across cell faces.
+ * table_size[l] need not be a power of two, in any of the hash-grid entry points: hashed levels then index with
+ * hash % table_size (a mask for powers of two), and the scatters handle a ragged last table slice. */
 int lnrf_hashgrid_jvp(const lnrf_hashgrid_desc* desc, const float* tables, const float* x, const float* u,
                       int64_t m, float* enc_t, lnrf_stream_t stream);
 int lnrf_hashgrid_input_grad(const lnrf_hashgrid_desc* desc, const float* tables, const float* x, int64_t m,

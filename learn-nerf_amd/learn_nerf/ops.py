@@ -332,8 +332,6 @@ def hashgrid_input_grad(desc, tables: torch.Tensor, x: torch.Tensor, g_enc_t: to
 
 
 def hashgrid_bwd_dir(desc, x: torch.Tensor, u: torch.Tensor, g_enc_t: torch.Tensor, g_tables: torch.Tensor):
-    import ctypes
-
     hashgrid_bwd(desc, x, g_enc_t, g_tables, u=u)
 
 

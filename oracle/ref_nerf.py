@@ -91,12 +91,13 @@ def ref_nerf_layer_dims(input_layers=5, mid_layers=4, hidden_dim=256, color_laye
     return dims
 
 
-def ref_nerf_base(spatial_block, directional_block, x: torch.Tensor, d: torch.Tensor, sh_degree: int):
-    """RefNERFBase.__call__ (ref_nerf.py:35-77) for arbitrary spatial / directional blocks."""
-    xr = x if x.requires_grad else x.clone().requires_grad_(True)
-    out = spatial_block(xr)
-    (real_normal,) = torch.autograd.grad(-out[:, 0].sum(), xr, create_graph=True)  # ref_nerf.py:38-42
-    real_normal = _safe_normalize(real_normal)
+def ref_nerf_head(spatial_out: torch.Tensor, n_raw: torch.Tensor, d: torch.Tensor, sh_degree: int):
+    """Everything of RefNERFBase.__call__ between the spatial and the directional block (ref_nerf.py:43-62, 72-75).
+    spatial_out [N, >= 9], n_raw [N, 3] (the unnormalised analytic normal -d out0/dx), d [N, 3] ->
+    density [N,1], diffuse [N,3], spectral [N,1], tail [N, sh^2 + 1] = [IDE(reflection, roughness), -d.n],
+    aux [N, 2] = [normal_mse, neg_normal]."""
+    out = spatial_out
+    real_normal = _safe_normalize(n_raw)
     density = torch.exp(out[:, 0:1])  # :45-48
     diffuse = torch.sigmoid(out[:, 1:4] - math.log(3))  # :52
     spectral = torch.sigmoid(out[:, 4:5])
@@ -105,13 +106,28 @@ def ref_nerf_base(spatial_block, directional_block, x: torch.Tensor, d: torch.Te
     reflection = d - 2 * normal * (d * normal).sum(dim=-1, keepdim=True)  # :59
     enc = integrated_directional_encoding(sh_degree, reflection, roughness)
     normal_dot = (-d * normal).sum(dim=-1, keepdim=True)
-    dir_input = torch.cat([out, enc, normal_dot], dim=1)  # :63 (the WHOLE spatial_out, not just the bottleneck)
+    tail = torch.cat([enc, normal_dot], dim=1)
+    aux = torch.stack([((normal - real_normal) ** 2).sum(dim=-1),  # :72-75
+                       torch.clamp((normal * d).sum(dim=-1), min=0.0) ** 2], dim=1)
+    return density, diffuse, spectral, tail, aux
+
+
+def ref_nerf_color(dir_out: torch.Tensor, spectral: torch.Tensor, diffuse: torch.Tensor) -> torch.Tensor:
+    """ref_nerf.py:65-71: dir_out [N,3], spectral [N,1], diffuse [N,3] -> rgb [N,3] in [-1, 1]."""
+    spectral_color = torch.sigmoid(dir_out)
+    return linear_rgb_to_srgb(_leaky_clip(spectral_color * spectral + diffuse)) * 2 - 1
+
+
+def ref_nerf_base(spatial_block, directional_block, x: torch.Tensor, d: torch.Tensor, sh_degree: int):
+    """RefNERFBase.__call__ (ref_nerf.py:35-77) for arbitrary spatial / directional blocks."""
+    xr = x if x.requires_grad else x.clone().requires_grad_(True)
+    out = spatial_block(xr)
+    (n_raw,) = torch.autograd.grad(-out[:, 0].sum(), xr, create_graph=True)  # ref_nerf.py:38-42
+    density, diffuse, spectral, tail, aux = ref_nerf_head(out, n_raw, d, sh_degree)
+    dir_input = torch.cat([out, tail], dim=1)  # :63 (the WHOLE spatial_out, not just the bottleneck)
     dir_output = directional_block(dir_input)
-    spectral_color = torch.sigmoid(dir_output)
-    full_color = linear_rgb_to_srgb(_leaky_clip(spectral_color * spectral + diffuse)) * 2 - 1  # :67-71
-    aux = dict(normal_mse=((normal - real_normal) ** 2).sum(dim=-1),  # :72-75
-               neg_normal=torch.clamp((normal * d).sum(dim=-1), min=0.0) ** 2)
-    return density, full_color, aux
+    full_color = ref_nerf_color(dir_output, spectral, diffuse)
+    return density, full_color, dict(normal_mse=aux[:, 0], neg_normal=aux[:, 1])
 
 
 def ref_nerf_model(flat: torch.Tensor, x: torch.Tensor, d: torch.Tensor, sh_degree=4, input_layers=5, mid_layers=4,
