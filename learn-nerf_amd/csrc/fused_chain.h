@@ -174,6 +174,12 @@ struct Ring {
   }
 };
 
+template <int COUNT>
+struct LinSeq {  // a stream consumed front to back without padding
+  static constexpr int count = COUNT;
+  static constexpr int at(int c) { return c; }
+};
+
 // n fp32 biases, global -> the LDS block bias_acc() reads, by the NT threads of the workgroup (the caller's barrier
 // publishes them)
 template <int NT>

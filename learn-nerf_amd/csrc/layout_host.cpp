@@ -1,11 +1,12 @@
 // layout_host.cpp — host build of the index maps of the fused NeRF kernels (nerf_layout.h) and of the
 // positional-encoding sincos (fast_math.h), so that tests/test_nerf_layout.py can run the exact packing /
 // fragment logic on the CPU (no GPU needed) with an MFMA emulator; and of the weight-gradient problem lists and their
-// gradient-vector addressing (nerf_wgrad.h).
+// gradient-vector addressing (nerf_wgrad.h); and of the tables and pack walks of the fused InstantNGPModel MLP (ngp_layout.h).
 #include <stdint.h>
 
 #include "fast_math.h"
 #include "nerf_wgrad.h"
+#include "ngp_layout.h"
 
 using namespace lnrf;
 
@@ -40,6 +41,41 @@ static int64_t wgrad_count_owners(const WgradProblem& pb, int32_t* count, int64_
     }
   return outside;
 }
+
+// What the end of ngp_mlp_kernel<NE, true> stores for problem P of kNgpWgrad (its `flush`: wave w4 of the layer's half, lane
+// (colr, hh), bias sum and accumulator register qq): adds 1 to count[part * n + i] for every float i of row (workgroup,
+// part) of the partial-sum buffer it writes; returns how many fall outside [0, n).
+// KEEP IN STEP with `flush` in ngp_mlp.hip: this is a copy of its arithmetic (the table, the argument builder and
+// NgpWgradEpi are shared); behind a shared function the persistent backward no longer compiles to the same code.
+template <int P>
+static int64_t ngp_count_owners(const NgpWgradProblem& pb, int64_t dense_off, int32_t* count, int64_t n) {
+  constexpr int NO = kNgpWgrad[P].nyf / 2, NT = ngp_wgrad_tiles(P);
+  int64_t outside = 0;
+  auto hit = [&](int part, int64_t i) {
+    if (i >= 0 && i < n) ++count[part * n + i];
+    else ++outside;
+  };
+  for (int w4 = 0; w4 < 4; ++w4)
+    for (int lane = 0; lane < 64; ++lane) {
+      const int colr = lane & 31, hh = lane >> 5;
+      const int tile_id = w4 % NT, part = w4 / NT;
+      const int it = tile_id / NO, ot = tile_id % NO;
+      int out_idx = -1, out_dim = 1;
+      int64_t w_off = 0, b_off = 0;
+      NgpWgradEpi::cols(pb, ot, colr, out_idx, out_dim, w_off, b_off);
+      w_off -= dense_off;
+      b_off -= dense_off;
+      if (it == 0 && hh == 0 && out_idx >= 0) hit(part, b_off + out_idx);
+      for (int qq = 0; qq < 16; ++qq) {
+        const int r = ngp_acc_row(qq, hh);
+        const int f = 2 * it + (r >> 4);
+        const int in_idx = NgpWgradEpi::row(pb, f, r & 15);
+        if (out_idx >= 0 && in_idx >= 0) hit(part, w_off + (int64_t)in_idx * out_dim + out_idx);
+      }
+    }
+  return outside;
+}
+static bool ngp_enc_dim_ok(int enc_dim) { return enc_dim >= 1 && enc_dim <= 32; }
 
 extern "C" {
 int lnrf_host_fwd_frags(void) { return kFwdFrags; }
@@ -143,6 +179,51 @@ int lnrf_host_wgrad_list(int which, int64_t n_tiles, int32_t* out) {
     }
   }
   return list.args.n_problems;
+}
+// ---- fused InstantNGPModel MLP (ngp_layout.h); parameter indices are relative to the first Dense parameter ----
+// The index array of a stream for enc_dim = L*F encoding features: stream 0 forward, 1 transposed (both over the 48
+// fragments of the blob, out[(g * 64 + lane) * 8 + j], -1 outside their own fragments), 2 bias block (out[i]).  Returns
+// its length, -1 for an unknown stream or enc_dim.  out == NULL: length only.
+int64_t lnrf_host_ngp_stream_indices(int stream, int enc_dim, int32_t* out) {
+  if (stream < 0 || stream > 2 || !ngp_enc_dim_ok(enc_dim)) return -1;
+  const NgpOffsets off = ngp_offsets(enc_dim, 0);
+  const int ne = ngp_ne(enc_dim);
+  const int64_t n = stream == 2 ? kNgpBiasFloats : (int64_t)kNgpStreamFrags * 512;
+  for (int64_t e = 0; out && e < n; ++e) {
+    const int g = (int)(e >> 9), lane = (int)((e >> 3) & 63), j = (int)(e & 7);
+    out[e] = (int32_t)(stream == 0 ? ngp_fwd_stream_index(g, lane, j, off, enc_dim, ne)
+                     : stream == 1 ? ngp_bwd_stream_index(g, lane, j, off, enc_dim, ne) : ngp_bias_index((int)e, off));
+  }
+  return n;
+}
+// what 0 bias block of the blob, 1 its size, 2 bias block of the split blob, 3 its size (bytes), 4 / 5 fragments of the
+// stream / fragment pairs of the split stream, 6 k-parts a partial-sum row is kept for
+int64_t lnrf_host_ngp_pack_offset(int what) {
+  const int64_t v[7] = {kNgpPackBiasOff, kNgpPackBytes, kNgpSplitBiasOff, kNgpSplitBytes, kNgpStreamFrags,
+                        kNgpSplitMaxFrags / 2, kNgpMaxParts};
+  return what >= 0 && what < 7 ? v[what] : -1;
+}
+// The weight-gradient stores of one workgroup of the persistent backward, through the production table, argument
+// builder and addressing, with the Dense block at a non-zero dense_offset: count[part * n + i] (kNgpMaxParts planes of n)
+// += 1 per store to float i of the row of k-part `part`; returns the stores outside [0, n), -1 for a bad enc_dim.
+int64_t lnrf_host_ngp_wgrad_owners(int enc_dim, int32_t* count, int64_t n) {
+  if (!ngp_enc_dim_ok(enc_dim)) return -1;
+  const int64_t dense_off = 1001;
+  const NgpWgradArgs a = ngp_wgrad_args(ngp_offsets(enc_dim, dense_off), enc_dim);
+  return ngp_count_owners<0>(a.p[0], dense_off, count, n) + ngp_count_owners<1>(a.p[1], dense_off, count, n) +
+         ngp_count_owners<2>(a.p[2], dense_off, count, n) + ngp_count_owners<3>(a.p[3], dense_off, count, n) +
+         ngp_count_owners<4>(a.p[4], dense_off, count, n);
+}
+// out[4 i ..]: Dense layer, float range [lo, hi) relative to dense_offset and k-parts of problem i of the reduce launch;
+// returns the Dense parameter count
+int lnrf_host_ngp_parts_plan(int enc_dim, int32_t* out) {
+  if (!ngp_enc_dim_ok(enc_dim)) return -1;
+  const NgpPartsPlan pl = ngp_parts_plan(ngp_offsets(enc_dim, 1001), 1001);
+  for (int i = 0; i < kNgpLayers; ++i) {
+    int32_t* o = out + 4 * i;
+    o[0] = kNgpWgrad[i].layer; o[1] = pl.lo[i]; o[2] = pl.hi[i]; o[3] = pl.parts[i];
+  }
+  return ngp_dense_params(enc_dim);
 }
 int64_t lnrf_host_wgrad_owners(int which, int64_t n_tiles, int32_t* count, int64_t n) {
   const WgradList list = wgrad_list_of(which, n_tiles);

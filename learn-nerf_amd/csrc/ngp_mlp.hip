@@ -8,47 +8,42 @@
 // goes through the shared LDS ring.  The network is so small that the backward kernel recomputes the
 // forward (26 MFMAs) instead of reading saved activations, then runs the transposed chain, writes
 // d loss / d enc feature-major for the hash-grid scatter, and forms the weight gradients in the same
-// launch (see NgpWgradProblem).
+// launch.  All index arithmetic lives in ngp_layout.h.
 // Precision: bf16 operands, fp32 accumulate, fp32 bias / activations / directional encoding.
 
 #include "fused_chain.h"
+#include "ngp_layout.h"
 
 namespace lnrf {
 
-constexpr int kNgpLayers = 5;
-constexpr int kNgpHidden = 64, kNgpDensityDim = 16, kNgpDembDim = 24;
-constexpr int kNgpStreamFrags = 48;                               // 3 ring stages
-constexpr int kNgpBiasFloats = 256;
-constexpr int kNgpPackBiasOff = kNgpStreamFrags * kFragBytes;
-constexpr int kNgpPackBytes = kNgpPackBiasOff + kNgpBiasFloats * 4;
 constexpr int kNgpLds = kRingBytes + 1024;
+template <int N>
+using Int = std::integral_constant<int, N>;
+template <int L>
+using NgpDense = Int<ngp_wgrad_problem(L)>;  // Dense_L's row of the weight-gradient table
 
-// forward layer l: k-steps, 32-row out tiles, first fragment (consumption order == stream order)
-constexpr int ngp_fwd_nk(int l, int ne) { return l == 0 ? ne : (l == 2 ? 3 : 4); }
-constexpr int ngp_fwd_no(int l) { return (l == 1 || l == 4) ? 1 : 2; }
-constexpr int ngp_fwd_base(int l, int ne) {
-  int b = 0;
-  for (int i = 0; i < l; ++i) b += ngp_fwd_nk(i, ne) * ngp_fwd_no(i);
-  return b;
+// forward layer L / backward step T of the chain, shaped by the tables of ngp_layout.h
+template <int NE, int L, class RING, class GetB, class Epi>
+__device__ __forceinline__ void ngp_fwd_layer(RING& ring, int h, GetB getb, Epi epi) {
+  chain_layer<ngp_fwd_base(L, NE), ngp_fwd_nk(L, NE), ngp_fwd_no(L)>(
+      ring, [&](auto o_) { return bias_acc(ngp_bias_base(L) + 32 * decltype(o_)::value, h); }, getb, epi);
 }
-constexpr int ngp_fwd_count(int ne) { return ngp_fwd_base(kNgpLayers, ne); }
-// backward step t applies Dense_{4-t}^T
-constexpr int ngp_bwd_nk(int t) { return (t == 0 || t == 3) ? 1 : 4; }
-constexpr int ngp_bwd_no(int t) { return (t == 2 || t == 4) ? 1 : 2; }
-constexpr int ngp_bwd_base(int t, int ne) {
-  int b = ngp_fwd_count(ne);
-  for (int i = 0; i < t; ++i) b += ngp_bwd_nk(i) * ngp_bwd_no(i);
-  return b;
+template <int NE, int T, class RING, class GetB, class Epi>
+__device__ __forceinline__ void ngp_bwd_layer(RING& ring, GetB getb, Epi epi) {
+  chain_layer<ngp_bwd_base(T, NE), ngp_bwd_nk(T), ngp_bwd_no(T)>(ring, [&](auto) { return zero_acc(); }, getb, epi);
 }
-constexpr int ngp_total_count(int ne) { return ngp_bwd_base(kNgpLayers, ne); }
-constexpr int ngp_bias_base(int l) { return l == 0 ? 0 : (l == 1 ? 64 : (l == 2 ? 96 : (l == 3 ? 160 : 224))); }
-__host__ __device__ constexpr int ngp_out_dim(int l) { return l == 1 ? kNgpDensityDim : (l == 4 ? 3 : kNgpHidden); }
 
-template <int NE, bool BWD>
-struct NgpSeq {
-  static constexpr int count = BWD ? ngp_total_count(NE) : ngp_fwd_count(NE);
-  static constexpr int at(int c) { return c; }
-};
+// out tile O of a 64-wide relu layer -> k-steps 2 O, 2 O + 1 of the next layer's B operand
+template <int O>
+__device__ __forceinline__ void relu_frags(const f32x16& acc, bf16x8 (&dst)[4]) {
+  dst[2 * O] = acc_to_frag<0, true>(acc);
+  dst[2 * O + 1] = acc_to_frag<1, true>(acc);
+}
+template <int O>
+__device__ __forceinline__ void relu_frags_split(const f32x16& acc, bf16x8 (&hi)[4], bf16x8 (&lo)[4]) {
+  acc_to_frag_split<0, true>(acc, hi[2 * O], lo[2 * O]);
+  acc_to_frag_split<1, true>(acc, hi[2 * O + 1], lo[2 * O + 1]);
+}
 
 // dh * relu'(h): keep accumulator registers 8S..8S+7 where the bf16 activation fragment is non-zero
 template <int S>
@@ -63,6 +58,11 @@ __device__ __forceinline__ bf16x8 masked_by(const f32x16& acc, const bf16x8& ref
   }
   return f;
 }
+template <int O>
+__device__ __forceinline__ void masked_frags(const f32x16& acc, const bf16x8 (&ref)[4], bf16x8 (&dst)[4]) {
+  dst[2 * O] = masked_by<0>(acc, ref[2 * O]);
+  dst[2 * O + 1] = masked_by<1>(acc, ref[2 * O + 1]);
+}
 
 // Backward: the weight gradients are formed inside the kernel.  The model has 10 K parameters, so a
 // workgroup can keep its share of dW in registers for the whole launch: the workgroups are persistent (one per CU,
@@ -71,39 +71,8 @@ __device__ __forceinline__ bf16x8 masked_by(const f32x16& acc, const bf16x8& ref
 // then every wave accumulates ONE 32x32 tile of that layer's dW over its share of the 8 steps (transposed
 // ds_read_b64_tr_b16 reads) and the tiles leave once, at the end of the launch (plain stores).  This removes the
 // 34 KiB per tile of X / dy dumps (written and read back: 2.3 GB per step at 4096 rays) and a second launch.
-struct NgpWgradProblem {
-  int unused_[6];          // not read; keeps the kernel's argument layout
-  int out_dim;             // columns of the Flax kernel (= valid dy features)
-  unsigned w_lo, w_hi, b_lo, b_hi;  // float offsets of kernel / bias in the gradient vector (64-bit, split)
-  int rb0, rb1, rb2, rb3;  // per X fragment: first kernel row ...
-  int rv0, rv1, rv2, rv3;  // ... and how many of its 16 features are real (scalars: keeps the struct in SGPRs)
-};
-struct NgpWgradArgs {
-  NgpWgradProblem p[kNgpLayers];
-};
-struct NgpWgradEpi {
-  static __device__ __forceinline__ void cols(const NgpWgradProblem& pb, int ot, int colr, int& out_idx,
-                                              int& out_dim, int64_t& w_off, int64_t& b_off) {
-    const int idx = 32 * ot + colr;
-    out_idx = idx < pb.out_dim ? idx : -1;
-    out_dim = pb.out_dim;
-    w_off = (int64_t)(((uint64_t)pb.w_hi << 32) | pb.w_lo);
-    b_off = (int64_t)(((uint64_t)pb.b_hi << 32) | pb.b_lo);
-  }
-  static __device__ __forceinline__ int row(const NgpWgradProblem& pb, int f, int r16) {
-    const int base = f == 0 ? pb.rb0 : (f == 1 ? pb.rb1 : (f == 2 ? pb.rb2 : pb.rb3));
-    const int nv = f == 0 ? pb.rv0 : (f == 1 ? pb.rv1 : (f == 2 ? pb.rv2 : pb.rv3));
-    return r16 < nv ? base + r16 : -1;
-  }
-};
-// k-parts of the backward per weight-gradient problem (host table order: Dense_3, Dense_2, Dense_1, Dense_4,
-// Dense_0): a layer with NT < 4 dW tiles is dealt to its four waves as NT tiles x 4 / NT parts of the group's 256
-// evaluations, and every part has its own row in the partial-sum buffer
-constexpr int kNgpMaxParts = 4;
-__host__ __device__ constexpr int ngp_wgrad_parts(int problem) { return (problem == 0 || problem == 1) ? 1 : 2; }
-struct NgpPartsPlan {
-  int lo[kNgpLayers], hi[kNgpLayers], parts[kNgpLayers];  // float range [lo, hi) relative to dense_offset
-};
+// Which waves accumulate which layer in which slot is kNgpWgrad (ngp_layout.h).
+
 // grads[dense_off + p] += sum over workgroups and the layer's k-parts of wparts[(wg, part)][p].  One workgroup folds 32
 // neighbouring parameters: thread (slice s, parameter) sums the rows of slice s of the workgroups in order, the eight
 // slice sums meet in LDS and are added in order by slice 0, which owns the parameter (plain read-modify-write).  Every
@@ -147,9 +116,9 @@ template <int NE, bool BWD>
 __global__ __launch_bounds__(kThreads) void ngp_mlp_kernel(
     const char* __restrict__ packed, const float* __restrict__ enc_t, const float* __restrict__ d_g, int lf,
     int64_t M, int64_t n_tiles, float* __restrict__ density, float* __restrict__ rgb,
-    const float* __restrict__ g_density, const float* __restrict__ g_rgb, char* __restrict__ /* not read */,
-    float* __restrict__ g_enc_t, float* __restrict__ lmax_parts = nullptr, NgpWgradArgs wargs = NgpWgradArgs{},
-    float* __restrict__ wparts = nullptr, int pstride = 0, int64_t dense_off = 0) {
+    const float* __restrict__ g_density, const float* __restrict__ g_rgb, float* __restrict__ g_enc_t,
+    float* __restrict__ lmax_parts = nullptr, NgpWgradArgs wargs = NgpWgradArgs{}, float* __restrict__ wparts = nullptr,
+    int pstride = 0, int64_t dense_off = 0) {
   // backward: running max |d loss / d enc| of the rows this lane writes, 8 slots (rows 4h + 8j + {0,1} / + {2,3} are
   // the two features of levels 2h + 4j / 2h + 4j + 1): the fixed-point scale of the scatter pass.  The persistent
   // kernel keeps the slots in LDS (32 bytes per lane, its registers are full), reduces them once at the end
@@ -167,15 +136,12 @@ __global__ __launch_bounds__(kThreads) void ngp_mlp_kernel(
   const int c = lane & 31, h = lane >> 5;
   stage_bias<kThreads>(packed + kNgpPackBiasOff, kNgpBiasFloats);
   if (tid < 16) s_lmax[tid] = 0u;
-  // persistent accumulators of the backward.  The layers are dealt to the two halves of the workgroup so that a
-  // wave carries at most three dW tiles (five would not fit next to the chain's fragments): waves 0-3 take
-  // Dense_3 (slot 0), Dense_4 (slot 1), Dense_0 (slot 2); waves 4-7 take Dense_2 (slot 0), Dense_1 (slot 1).
-  constexpr int kWSlots = 3;
-  f32x16 wacc[BWD ? kWSlots : 1];
-  float wbias[BWD ? kWSlots : 1];
+  // persistent accumulators of the backward: kNgpWgrad says which half of the workgroup and which slot a layer gets
+  f32x16 wacc[BWD ? kNgpWSlots : 1];
+  float wbias[BWD ? kNgpWSlots : 1];
   if constexpr (BWD) {
 #pragma unroll
-    for (int i = 0; i < kWSlots; ++i) {
+    for (int i = 0; i < kNgpWSlots; ++i) {
       wacc[i] = zero_acc();
       wbias[i] = 0.0f;
     }
@@ -185,7 +151,7 @@ __global__ __launch_bounds__(kThreads) void ngp_mlp_kernel(
   const int64_t tile = group * kWaves + wave;
   const int64_t m = tile * kTileCols + c;
   const bool valid = m < M;
-  using Seq = NgpSeq<NE, BWD>;
+  using Seq = LinSeq<BWD ? ngp_total_count(NE) : ngp_fwd_count(NE)>;
   Ring<(Seq::count + kStageFrags - 1) / kStageFrags, Seq> ring;
 #ifdef LNRF_TIMELINE
   ring.tl.buf = g_ngp_timeline_buf;
@@ -197,7 +163,7 @@ __global__ __launch_bounds__(kThreads) void ngp_mlp_kernel(
   if constexpr (BWD) __syncthreads();  // previous group's LDS reads (ring, staging) are finished
   LNRF_TL_STAMP(ring);  // 1: after the top barrier
 
-  // encoding fragments: k slot (ks, h, j) <-> feature 16 ks + 8 (j >> 2) + 4 h + (j & 3) (row of enc_t).
+  // encoding fragments: k slot (ks, h, j) <-> feature hidden_feat(ks, h, j) (row of enc_t; spelled out).
   // All loads are issued before the first use: clamped addresses instead of branches, and the row stride re-read
   // through an opaque copy so that the 16 row addresses are computed here instead of being hoisted out of the group
   // loop and spilled (that version waited for 32 scratch / global round trips in a row: 12 us of a 32 us group).
@@ -270,15 +236,14 @@ __global__ __launch_bounds__(kThreads) void ngp_mlp_kernel(
   auto stage_frag = [&](int f, const bf16x8& v) {
     *reinterpret_cast<uint4*>(stage + f * kFragBytes + dump_lane_off(f, c, h)) = frag_to_bits(v);
   };
-  auto wgrad_layer = [&](auto slot_, auto half_, auto nxf_, auto nyf_) {
-    constexpr int SLOT = decltype(slot_)::value, HALF = decltype(half_)::value;
-    constexpr int NXF = decltype(nxf_)::value, NYF = decltype(nyf_)::value;
-    constexpr int NI = NXF / 2, NO = NYF / 2, NT = NI * NO;  // tiles of this layer's dW
-    constexpr int STEPS = 2 * NT;                            // 4 waves = NT tiles x (4 / NT) k-parts of 8 / (4 / NT) steps
+  auto wgrad_layer = [&](auto p_) {
+    constexpr int P = decltype(p_)::value, SLOT = kNgpWgrad[P].slot, HALF = kNgpWgrad[P].half, NXF = kNgpWgrad[P].nxf;
+    constexpr int STEPS = 2 * ngp_wgrad_tiles(P);  // 4 waves = NT tiles x (4 / NT) k-parts of 8 / (4 / NT) steps
     LNRF_TL_STAMP(ring);                                     // staged, arrive
     __syncthreads();                                         // all 8 tiles staged
     LNRF_TL_STAMP(ring);                                     // released
     if ((wave >> 2) == HALF) {
+      constexpr int NO = kNgpWgrad[P].nyf / 2, NT = ngp_wgrad_tiles(P);
       const int w4 = wave & 3;
       const int tile_id = w4 % NT, part = w4 / NT;
       const int it = tile_id / NO, ot = tile_id % NO;
@@ -305,55 +270,35 @@ __global__ __launch_bounds__(kThreads) void ngp_mlp_kernel(
   bf16x8 h0[4], o16, c1[4], c2[4];
   float logit = 0.0f;
   // Dense_0 + relu
-  chain_layer<ngp_fwd_base(0, NE), NE, 2>(
-      ring, [&](auto o_) { return bias_acc(ngp_bias_base(0) + 32 * decltype(o_)::value, h); },
-      [&](auto k_) -> bf16x8 { return ef[decltype(k_)::value]; },
-      [&](auto o_, const f32x16& acc) {
-        constexpr int o = decltype(o_)::value;
-        h0[2 * o] = acc_to_frag<0, true>(acc);
-        h0[2 * o + 1] = acc_to_frag<1, true>(acc);
-      });
+  ngp_fwd_layer<NE, 0>(ring, h, [&](auto k_) -> bf16x8 { return ef[decltype(k_)::value]; },
+                       [&](auto o_, const f32x16& acc) { relu_frags<decltype(o_)::value>(acc, h0); });
   // Dense_1 (linear): 16 features = rows 0..15 of the tile; density logit = feature 0
-  chain_layer<ngp_fwd_base(1, NE), 4, 1>(
-      ring, [&](auto) { return bias_acc(ngp_bias_base(1), h); },
-      [&](auto k_) -> bf16x8 { return h0[decltype(k_)::value]; },
-      [&](auto, const f32x16& acc) {
-        o16 = acc_to_frag<0, false>(acc);
-        logit = acc[0];
-      });
+  ngp_fwd_layer<NE, 1>(ring, h, [&](auto k_) -> bf16x8 { return h0[decltype(k_)::value]; },
+                       [&](auto, const f32x16& acc) {
+                         o16 = acc_to_frag<0, false>(acc);
+                         logit = acc[0];
+                       });
   const float dens = __expf(logit);  // instant_ngp.py:49, valid on lanes h == 0
   // Dense_2 + relu on [d_emb, out]
-  chain_layer<ngp_fwd_base(2, NE), 3, 2>(
-      ring, [&](auto o_) { return bias_acc(ngp_bias_base(2) + 32 * decltype(o_)::value, h); },
+  ngp_fwd_layer<NE, 2>(
+      ring, h,
       [&](auto k_) -> bf16x8 {
         constexpr int ks = decltype(k_)::value;
         if constexpr (ks < 2) return de[ks];
         else return o16;
       },
-      [&](auto o_, const f32x16& acc) {
-        constexpr int o = decltype(o_)::value;
-        c1[2 * o] = acc_to_frag<0, true>(acc);
-        c1[2 * o + 1] = acc_to_frag<1, true>(acc);
-      });
+      [&](auto o_, const f32x16& acc) { relu_frags<decltype(o_)::value>(acc, c1); });
   // Dense_3 + relu
-  chain_layer<ngp_fwd_base(3, NE), 4, 2>(
-      ring, [&](auto o_) { return bias_acc(ngp_bias_base(3) + 32 * decltype(o_)::value, h); },
-      [&](auto k_) -> bf16x8 { return c1[decltype(k_)::value]; },
-      [&](auto o_, const f32x16& acc) {
-        constexpr int o = decltype(o_)::value;
-        c2[2 * o] = acc_to_frag<0, true>(acc);
-        c2[2 * o + 1] = acc_to_frag<1, true>(acc);
-      });
+  ngp_fwd_layer<NE, 3>(ring, h, [&](auto k_) -> bf16x8 { return c1[decltype(k_)::value]; },
+                       [&](auto o_, const f32x16& acc) { relu_frags<decltype(o_)::value>(acc, c2); });
   // Dense_4 + tanh
   float y[3] = {0, 0, 0};
-  chain_layer<ngp_fwd_base(4, NE), 4, 1>(
-      ring, [&](auto) { return bias_acc(ngp_bias_base(4), h); },
-      [&](auto k_) -> bf16x8 { return c2[decltype(k_)::value]; },
-      [&](auto, const f32x16& acc) {
-        y[0] = tanhf(acc[0]);
-        y[1] = tanhf(acc[1]);
-        y[2] = tanhf(acc[2]);
-      });
+  ngp_fwd_layer<NE, 4>(ring, h, [&](auto k_) -> bf16x8 { return c2[decltype(k_)::value]; },
+                       [&](auto, const f32x16& acc) {
+                         y[0] = tanhf(acc[0]);
+                         y[1] = tanhf(acc[1]);
+                         y[2] = tanhf(acc[2]);
+                       });
   if constexpr (!BWD) {
     if (h == 0 && valid) {
       density[m] = dens;
@@ -375,75 +320,58 @@ __global__ __launch_bounds__(kThreads) void ngp_mlp_kernel(
       static_for<4>([&](auto i_) { stage_frag(decltype(i_)::value, c2[decltype(i_)::value]); });
       stage_frag(4, dy4);
       stage_frag(5, zero_frag());
-      wgrad_layer(std::integral_constant<int, 1>{}, std::integral_constant<int, 0>{}, std::integral_constant<int, 4>{}, std::integral_constant<int, 2>{});  // Dense_4: waves 0-3, slot 1
+      wgrad_layer(NgpDense<4>{});
     }
 
     bf16x8 dy3[4], dy2[4], dy1, dy0[4];
     // T0: Dense_4^T -> dc2, relu mask of c2
-    chain_layer<ngp_bwd_base(0, NE), 1, 2>(
-        ring, [&](auto) { return zero_acc(); }, [&](auto) -> bf16x8 { return dy4; },
-        [&](auto o_, const f32x16& acc) {
-          constexpr int o = decltype(o_)::value;
-          dy3[2 * o] = masked_by<0>(acc, c2[2 * o]);
-          dy3[2 * o + 1] = masked_by<1>(acc, c2[2 * o + 1]);
-        });
+    ngp_bwd_layer<NE, 0>(ring, [&](auto) -> bf16x8 { return dy4; },
+                         [&](auto o_, const f32x16& acc) { masked_frags<decltype(o_)::value>(acc, c2, dy3); });
     {  // Dense_3: X = c1, dy = dy3
       static_for<4>([&](auto i_) {
         stage_frag(decltype(i_)::value, c1[decltype(i_)::value]);
         stage_frag(4 + decltype(i_)::value, dy3[decltype(i_)::value]);
       });
-      wgrad_layer(std::integral_constant<int, 0>{}, std::integral_constant<int, 0>{}, std::integral_constant<int, 4>{}, std::integral_constant<int, 4>{});  // Dense_3: waves 0-3, slot 0
+      wgrad_layer(NgpDense<3>{});
     }
     // T1: Dense_3^T -> dc1, relu mask of c1
-    chain_layer<ngp_bwd_base(1, NE), 4, 2>(
-        ring, [&](auto) { return zero_acc(); }, [&](auto k_) -> bf16x8 { return dy3[decltype(k_)::value]; },
-        [&](auto o_, const f32x16& acc) {
-          constexpr int o = decltype(o_)::value;
-          dy2[2 * o] = masked_by<0>(acc, c1[2 * o]);
-          dy2[2 * o + 1] = masked_by<1>(acc, c1[2 * o + 1]);
-        });
+    ngp_bwd_layer<NE, 1>(ring, [&](auto k_) -> bf16x8 { return dy3[decltype(k_)::value]; },
+                         [&](auto o_, const f32x16& acc) { masked_frags<decltype(o_)::value>(acc, c1, dy2); });
     {  // Dense_2: X = [d_emb, out] (24 + 16 features in 4 fragments), dy = dy2
       stage_frag(0, de[0]);
       stage_frag(1, de[1]);
       stage_frag(2, o16);
       stage_frag(3, zero_frag());
       static_for<4>([&](auto i_) { stage_frag(4 + decltype(i_)::value, dy2[decltype(i_)::value]); });
-      wgrad_layer(std::integral_constant<int, 0>{}, std::integral_constant<int, 1>{}, std::integral_constant<int, 4>{}, std::integral_constant<int, 4>{});  // Dense_2: waves 4-7, slot 0
+      wgrad_layer(NgpDense<2>{});
     }
     // T2: Dense_2^T restricted to the rows of `out` (d_emb has no parameters upstream); the density
     // head adds d exp(out_0) to feature 0 (lane h == 0, register 0)
-    chain_layer<ngp_bwd_base(2, NE), 4, 1>(
-        ring, [&](auto) { return zero_acc(); }, [&](auto k_) -> bf16x8 { return dy2[decltype(k_)::value]; },
-        [&](auto, const f32x16& acc) {
-          f32x16 t = acc;
-          t[0] += g_logit;
-          dy1 = acc_to_frag<0, false>(t);
-        });
+    ngp_bwd_layer<NE, 2>(ring, [&](auto k_) -> bf16x8 { return dy2[decltype(k_)::value]; },
+                         [&](auto, const f32x16& acc) {
+                           f32x16 t = acc;
+                           t[0] += g_logit;
+                           dy1 = acc_to_frag<0, false>(t);
+                         });
     {  // Dense_1: X = h0, dy = dy1
       static_for<4>([&](auto i_) { stage_frag(decltype(i_)::value, h0[decltype(i_)::value]); });
       stage_frag(4, dy1);
       stage_frag(5, zero_frag());
-      wgrad_layer(std::integral_constant<int, 1>{}, std::integral_constant<int, 1>{}, std::integral_constant<int, 4>{}, std::integral_constant<int, 2>{});  // Dense_1: waves 4-7, slot 1
+      wgrad_layer(NgpDense<1>{});
     }
     // T3: Dense_1^T -> dh0, relu mask of h0
-    chain_layer<ngp_bwd_base(3, NE), 1, 2>(
-        ring, [&](auto) { return zero_acc(); }, [&](auto) -> bf16x8 { return dy1; },
-        [&](auto o_, const f32x16& acc) {
-          constexpr int o = decltype(o_)::value;
-          dy0[2 * o] = masked_by<0>(acc, h0[2 * o]);
-          dy0[2 * o + 1] = masked_by<1>(acc, h0[2 * o + 1]);
-        });
+    ngp_bwd_layer<NE, 3>(ring, [&](auto) -> bf16x8 { return dy1; },
+                         [&](auto o_, const f32x16& acc) { masked_frags<decltype(o_)::value>(acc, h0, dy0); });
     {  // Dense_0: X = hash-grid encoding, dy = dy0
       stage_frag(0, ef[0]);
       if constexpr (NE > 1) stage_frag(1, ef[1]);
       else stage_frag(1, zero_frag());
       static_for<4>([&](auto i_) { stage_frag(2 + decltype(i_)::value, dy0[decltype(i_)::value]); });
-      wgrad_layer(std::integral_constant<int, 2>{}, std::integral_constant<int, 0>{}, std::integral_constant<int, 2>{}, std::integral_constant<int, 4>{});  // Dense_0: waves 0-3, slot 2
+      wgrad_layer(NgpDense<0>{});
     }
     // T4: Dense_0^T -> d loss / d enc, feature-major fp32 for the hash-grid scatter
-    chain_layer<ngp_bwd_base(4, NE), 4, 1>(
-        ring, [&](auto) { return zero_acc(); }, [&](auto k_) -> bf16x8 { return dy0[decltype(k_)::value]; },
-        [&](auto, const f32x16& acc) {
+    ngp_bwd_layer<NE, 4>(
+        ring, [&](auto k_) -> bf16x8 { return dy0[decltype(k_)::value]; }, [&](auto, const f32x16& acc) {
           float tmax[8];
 #pragma unroll
           for (int i = 0; i < 8; ++i) tmax[i] = 0.0f;
@@ -480,12 +408,11 @@ __global__ __launch_bounds__(kThreads) void ngp_mlp_kernel(
     // (workgroup, k-part) in `wparts`; ngp_wparts_reduce_kernel folds the rows into the gradient vector.  (fp32
     // atomics straight into the gradient — 256 workgroups hitting the same 10 K addresses — cost 76 us per launch,
     // half of the coarse model's backward: same-line memory atomics retire one after the other.)
+    // KEEP IN STEP with ngp_count_owners (layout_host.cpp), the copy of this arithmetic that the CPU test walks.
     const int colr = lane & 31, hh = lane >> 5;
-    auto flush = [&](auto p_, auto slot_, auto half_, auto nxf_, auto nyf_) {
-      constexpr int P = decltype(p_)::value, SLOT = decltype(slot_)::value, HALF = decltype(half_)::value;
-      constexpr int NXF = decltype(nxf_)::value, NYF = decltype(nyf_)::value;
-      constexpr int NO = NYF / 2, NT = (NXF / 2) * NO;
-      static_assert(4 / NT == ngp_wgrad_parts(P), "k-parts per layer: host table of the reduce launch");
+    auto flush = [&](auto p_) {
+      constexpr int P = decltype(p_)::value, SLOT = kNgpWgrad[P].slot, HALF = kNgpWgrad[P].half;
+      constexpr int NO = kNgpWgrad[P].nyf / 2, NT = ngp_wgrad_tiles(P);
       if ((wave >> 2) != HALF) return;
       const NgpWgradProblem& pb = wargs.p[P];
       const int tile_id = (wave & 3) % NT, part = (wave & 3) / NT;
@@ -503,18 +430,14 @@ __global__ __launch_bounds__(kThreads) void ngp_mlp_kernel(
       }
       static_for<16>([&](auto q_) {
         constexpr int qq = decltype(q_)::value;
-        const int r = (qq & 3) + 8 * (qq >> 2) + 4 * hh;
+        const int r = ngp_acc_row(qq, hh);
         const int f = 2 * it + (r >> 4);
         const int in_idx = NgpWgradEpi::row(pb, f, r & 15);
         if (out_idx >= 0 && in_idx >= 0) row[w_off + (int64_t)in_idx * out_dim + out_idx] = wacc[SLOT][qq];
       });
     };
-    // (problem index of the host table, accumulator slot, workgroup half, X fragments, dy fragments)
-    flush(std::integral_constant<int, 0>{}, std::integral_constant<int, 0>{}, std::integral_constant<int, 0>{}, std::integral_constant<int, 4>{}, std::integral_constant<int, 4>{});  // Dense_3
-    flush(std::integral_constant<int, 3>{}, std::integral_constant<int, 1>{}, std::integral_constant<int, 0>{}, std::integral_constant<int, 4>{}, std::integral_constant<int, 2>{});  // Dense_4
-    flush(std::integral_constant<int, 4>{}, std::integral_constant<int, 2>{}, std::integral_constant<int, 0>{}, std::integral_constant<int, 2>{}, std::integral_constant<int, 4>{});  // Dense_0
-    flush(std::integral_constant<int, 1>{}, std::integral_constant<int, 0>{}, std::integral_constant<int, 1>{}, std::integral_constant<int, 4>{}, std::integral_constant<int, 4>{});  // Dense_2
-    flush(std::integral_constant<int, 2>{}, std::integral_constant<int, 1>{}, std::integral_constant<int, 1>{}, std::integral_constant<int, 4>{}, std::integral_constant<int, 2>{});  // Dense_1
+    flush(NgpDense<3>{}), flush(NgpDense<4>{}), flush(NgpDense<0>{});  // waves 0-3
+    flush(NgpDense<2>{}), flush(NgpDense<1>{});                        // waves 4-7
   }
 }
 
@@ -534,61 +457,12 @@ __global__ __launch_bounds__(256) void ngp_level_max_kernel(const float* __restr
 }
 
 // ---------------------------------------------------------------------------------------------
-// weight packing: flat fp32 parameters -> bf16 A-fragment stream (forward then transposed) + fp32 biases
-// ---------------------------------------------------------------------------------------------
-struct NgpOffsets {
-  int64_t w[kNgpLayers], b[kNgpLayers];
-};
-
-// parameter feeding element (lane, j) of forward A-fragment g (stream order = consumption order); -1 = zero padding
-__device__ __forceinline__ int64_t ngp_fwd_param_index(int g, int lane, int j, const NgpOffsets& off, int lf, int ne) {
-  const int r = lane & 31, hh = lane >> 5;
-  const int fo = 8 * (j >> 2) + 4 * hh + (j & 3);  // feature offset of k slot (hh, j) within its k-step
-  int l = 0;
-  for (int i = 1; i < kNgpLayers; ++i)
-    if (g >= ngp_fwd_base(i, ne)) l = i;
-  const int loc = g - ngp_fwd_base(l, ne), nk = ngp_fwd_nk(l, ne);
-  const int o = loc / nk, ks = loc % nk;
-  const int row = 32 * o + r, od = ngp_out_dim(l);
-  int k = -1;
-  if (l == 0) k = (16 * ks + fo < lf) ? 16 * ks + fo : -1;
-  else if (l == 2) k = ks == 0 ? fo : (ks == 1 ? (fo < 8 ? 16 + fo : -1) : kNgpDembDim + fo);
-  else k = 16 * ks + fo;
-  return (row < od && k >= 0) ? off.w[l] + (int64_t)k * od + row : -1;
-}
-
-// ---------------------------------------------------------------------------------------------
 // Split-precision forward ("bf16x3", the render / evaluation path; instant_ngp.py:38-54 is fp32 in the reference): every
 // fp32 operand — weight, hash-grid feature, direction embedding, activation — is a bf16 pair (hi, lo) with hi + lo equal
 // to the value to 16 significant bits and every product is lo*hi + hi*lo + hi*hi on the bf16 MFMA with fp32 accumulation,
 // as nerf_fwd_split_kernel does for NeRFModel.  The whole stream ([hi, lo] per forward fragment: at most 52 KiB) is
 // staged in LDS once per persistent workgroup.
 // ---------------------------------------------------------------------------------------------
-constexpr int kNgpSplitMaxFrags = 2 * 26;
-constexpr int kNgpSplitBiasOff = kNgpSplitMaxFrags * kFragBytes;
-constexpr int kNgpSplitBytes = kNgpSplitBiasOff + kNgpBiasFloats * 4;
-
-__global__ void ngp_pack_split_kernel(const float* __restrict__ params, NgpOffsets off, int lf, int ne,
-                                      char* __restrict__ packed) {
-  const int total_w = kNgpSplitMaxFrags * 512;
-  const int total = total_w + kNgpBiasFloats;
-  for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < total; e += gridDim.x * blockDim.x) {
-    if (e < total_w) {
-      const int gg = e >> 9, lane = (e >> 3) & 63, j = e & 7;
-      const int g = gg >> 1;
-      const int64_t idx = g < ngp_fwd_count(ne) ? ngp_fwd_param_index(g, lane, j, off, lf, ne) : -1;
-      reinterpret_cast<__bf16*>(packed)[e] = split_half(param_or_zero(params, idx), gg & 1);
-    } else {
-      const int i = e - total_w;
-      int l = 0;
-      for (int k = 1; k < kNgpLayers; ++k)
-        if (i >= ngp_bias_base(k)) l = k;
-      const int loc = i - ngp_bias_base(l);
-      reinterpret_cast<float*>(packed + kNgpSplitBiasOff)[i] = loc < ngp_out_dim(l) ? params[off.b[l] + loc] : 0.0f;
-    }
-  }
-}
-
 template <int NE>
 __global__ __launch_bounds__(kThreads) void ngp_mlp_fwd_split_kernel(
     const char* __restrict__ packed3, const float* __restrict__ enc_t, const float* __restrict__ d_g, int lf, int64_t M,
@@ -617,8 +491,9 @@ __global__ __launch_bounds__(kThreads) void ngp_mlp_fwd_split_kernel(
     return acc;
   };
   // one layer: out tiles x k-steps, three MFMAs per product (small terms first)
-  auto layer = [&](auto g0_, auto nk_, auto no_, int bias0, auto&& bhi, auto&& blo, auto&& epi) {
-    constexpr int G0 = decltype(g0_)::value, NK = decltype(nk_)::value, NO = decltype(no_)::value;
+  auto layer = [&](auto l_, auto&& bhi, auto&& blo, auto&& epi) {
+    constexpr int L = decltype(l_)::value, bias0 = ngp_bias_base(L);
+    constexpr int G0 = ngp_fwd_base(L, NE), NK = ngp_fwd_nk(L, NE), NO = ngp_fwd_no(L);
     static_for<NO>([&](auto o_) {
       constexpr int o = decltype(o_)::value;
       f32x16 acc = bias_tile(bias0 + 32 * o);
@@ -644,7 +519,7 @@ __global__ __launch_bounds__(kThreads) void ngp_mlp_fwd_split_kernel(
       constexpr int ks = decltype(ks_)::value;
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
-        const int feat = 16 * ks + 8 * (j >> 2) + 4 * h + (j & 3);
+        const int feat = hidden_feat(ks, h, j);
         const float v = (valid && feat < lf) ? enc_t[(int64_t)(feat < lf ? feat : lf - 1) * M + mm] : 0.0f;
         split_store(v, ef_hi[ks], ef_lo[ks], j);
       }
@@ -659,7 +534,7 @@ __global__ __launch_bounds__(kThreads) void ngp_mlp_fwd_split_kernel(
       constexpr int ks = decltype(ks_)::value;
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
-        const int e = 16 * ks + 8 * (j >> 2) + 4 * h + (j & 3);
+        const int e = hidden_feat(ks, h, j);
         float v = 0.0f;
         if (e < kNgpDembDim) {
           const int cd = e >> 3, fr = e & 3;
@@ -673,25 +548,16 @@ __global__ __launch_bounds__(kThreads) void ngp_mlp_fwd_split_kernel(
     });
     bf16x8 h0h[4], h0l[4], o16h, o16l, c1h[4], c1l[4], c2h[4], c2l[4];
     float logit = 0.0f, y[3] = {0, 0, 0};
-    using I = std::integral_constant<int, 0>;
-    (void)sizeof(I);
-    layer(std::integral_constant<int, ngp_fwd_base(0, NE)>{}, std::integral_constant<int, NE>{}, std::integral_constant<int, 2>{},
-          ngp_bias_base(0), [&](auto k_) -> bf16x8 { return ef_hi[decltype(k_)::value]; },
+    layer(Int<0>{}, [&](auto k_) -> bf16x8 { return ef_hi[decltype(k_)::value]; },
           [&](auto k_) -> bf16x8 { return ef_lo[decltype(k_)::value]; },
-          [&](auto o_, const f32x16& acc) {
-            constexpr int o = decltype(o_)::value;
-            acc_to_frag_split<0, true>(acc, h0h[2 * o], h0l[2 * o]);
-            acc_to_frag_split<1, true>(acc, h0h[2 * o + 1], h0l[2 * o + 1]);
-          });
-    layer(std::integral_constant<int, ngp_fwd_base(1, NE)>{}, std::integral_constant<int, 4>{}, std::integral_constant<int, 1>{},
-          ngp_bias_base(1), [&](auto k_) -> bf16x8 { return h0h[decltype(k_)::value]; },
+          [&](auto o_, const f32x16& acc) { relu_frags_split<decltype(o_)::value>(acc, h0h, h0l); });
+    layer(Int<1>{}, [&](auto k_) -> bf16x8 { return h0h[decltype(k_)::value]; },
           [&](auto k_) -> bf16x8 { return h0l[decltype(k_)::value]; },
           [&](auto, const f32x16& acc) {
             acc_to_frag_split<0, false>(acc, o16h, o16l);
             logit = acc[0];
           });
-    layer(std::integral_constant<int, ngp_fwd_base(2, NE)>{}, std::integral_constant<int, 3>{}, std::integral_constant<int, 2>{},
-          ngp_bias_base(2),
+    layer(Int<2>{},
           [&](auto k_) -> bf16x8 {
             constexpr int ks = decltype(k_)::value;
             if constexpr (ks < 2) return de_hi[ks];
@@ -702,21 +568,11 @@ __global__ __launch_bounds__(kThreads) void ngp_mlp_fwd_split_kernel(
             if constexpr (ks < 2) return de_lo[ks];
             else return o16l;
           },
-          [&](auto o_, const f32x16& acc) {
-            constexpr int o = decltype(o_)::value;
-            acc_to_frag_split<0, true>(acc, c1h[2 * o], c1l[2 * o]);
-            acc_to_frag_split<1, true>(acc, c1h[2 * o + 1], c1l[2 * o + 1]);
-          });
-    layer(std::integral_constant<int, ngp_fwd_base(3, NE)>{}, std::integral_constant<int, 4>{}, std::integral_constant<int, 2>{},
-          ngp_bias_base(3), [&](auto k_) -> bf16x8 { return c1h[decltype(k_)::value]; },
+          [&](auto o_, const f32x16& acc) { relu_frags_split<decltype(o_)::value>(acc, c1h, c1l); });
+    layer(Int<3>{}, [&](auto k_) -> bf16x8 { return c1h[decltype(k_)::value]; },
           [&](auto k_) -> bf16x8 { return c1l[decltype(k_)::value]; },
-          [&](auto o_, const f32x16& acc) {
-            constexpr int o = decltype(o_)::value;
-            acc_to_frag_split<0, true>(acc, c2h[2 * o], c2l[2 * o]);
-            acc_to_frag_split<1, true>(acc, c2h[2 * o + 1], c2l[2 * o + 1]);
-          });
-    layer(std::integral_constant<int, ngp_fwd_base(4, NE)>{}, std::integral_constant<int, 4>{}, std::integral_constant<int, 1>{},
-          ngp_bias_base(4), [&](auto k_) -> bf16x8 { return c2h[decltype(k_)::value]; },
+          [&](auto o_, const f32x16& acc) { relu_frags_split<decltype(o_)::value>(acc, c2h, c2l); });
+    layer(Int<4>{}, [&](auto k_) -> bf16x8 { return c2h[decltype(k_)::value]; },
           [&](auto k_) -> bf16x8 { return c2l[decltype(k_)::value]; },
           [&](auto, const f32x16& acc) {
             y[0] = tanhf(acc[0]);
@@ -732,42 +588,21 @@ __global__ __launch_bounds__(kThreads) void ngp_mlp_fwd_split_kernel(
   }
 }
 
+// SPLIT: [hi, lo] pairs of the forward fragments (the render blob), else the 48-fragment stream; then the fp32 biases
+template <bool SPLIT>
 __global__ void ngp_pack_kernel(const float* __restrict__ params, NgpOffsets off, int lf, int ne,
                                 char* __restrict__ packed) {
-  const int total_frag_elems = kNgpStreamFrags * 512;
-  const int total = total_frag_elems + kNgpBiasFloats;
-  for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < total; e += gridDim.x * blockDim.x) {
-    if (e < total_frag_elems) {
-      const int g = e >> 9, lane = (e >> 3) & 63, j = e & 7;
-      const int r = lane & 31, hh = lane >> 5;
-      const int fo = 8 * (j >> 2) + 4 * hh + (j & 3);  // feature offset of k slot (hh, j) within its k-step
-      int64_t idx = -1;
-      const int nfwd = ngp_fwd_count(ne);
-      if (g < nfwd) {
-        idx = ngp_fwd_param_index(g, lane, j, off, lf, ne);
-      } else if (g < ngp_total_count(ne)) {
-        int t = 0;
-        for (int i = 1; i < kNgpLayers; ++i)
-          if (g >= ngp_bwd_base(i, ne)) t = i;
-        const int loc = g - ngp_bwd_base(t, ne), nk = ngp_bwd_nk(t);
-        const int o = loc / nk, ks = loc % nk;
-        const int l = 4 - t, od = ngp_out_dim(l);
-        // A[row = input feature of Dense_l][k = output feature of Dense_l] = W_l[row][k]
-        int row = 32 * o + r;
-        const int k = 16 * ks + fo;
-        if (l == 2) row = r < kNgpDensityDim ? kNgpDembDim + r : -1;  // only the rows fed by `out`
-        else if (l == 0) row = r < lf ? r : -1;
-        else if (row >= kNgpHidden) row = -1;
-        if (row >= 0 && k < od) idx = off.w[l] + (int64_t)row * od + k;
-      }
-      reinterpret_cast<__bf16*>(packed)[e] = (__bf16)param_or_zero(params, idx);
+  constexpr int total_w = (SPLIT ? kNgpSplitMaxFrags : kNgpStreamFrags) * 512;
+  for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < total_w + kNgpBiasFloats; e += gridDim.x * blockDim.x) {
+    if (e < total_w) {
+      const int g = SPLIT ? e >> 10 : e >> 9, lane = (e >> 3) & 63, j = e & 7;
+      const int64_t idx = SPLIT || g < ngp_fwd_count(ne) ? ngp_fwd_stream_index(g, lane, j, off, lf, ne)
+                                                         : ngp_bwd_stream_index(g, lane, j, off, lf, ne);
+      const float w = param_or_zero(params, idx);
+      reinterpret_cast<__bf16*>(packed)[e] = SPLIT ? split_half(w, (e >> 9) & 1) : (__bf16)w;
     } else {
-      const int i = e - total_frag_elems;
-      int l = 0;
-      for (int k = 1; k < kNgpLayers; ++k)
-        if (i >= ngp_bias_base(k)) l = k;
-      const int loc = i - ngp_bias_base(l);
-      reinterpret_cast<float*>(packed + kNgpPackBiasOff)[i] = loc < ngp_out_dim(l) ? params[off.b[l] + loc] : 0.0f;
+      float* bias = reinterpret_cast<float*>(packed + (SPLIT ? kNgpSplitBiasOff : kNgpPackBiasOff));
+      bias[e - total_w] = param_or_zero(params, ngp_bias_index(e - total_w, off));
     }
   }
 }
@@ -780,23 +615,11 @@ static bool ngp_supported(const lnrf_ngp_mlp_desc* d) {
   return d && d->hidden_dim == kNgpHidden && d->density_dim == kNgpDensityDim && d->density_layers == 1 &&
          d->color_layers == 2 && d->d_freqs == 4 && d->enc_dim >= 1 && d->enc_dim <= 32;
 }
-// padded to whole workgroups (8 waves): the kernels walk groups of 8 tiles
-static NgpOffsets ngp_offsets(const lnrf_ngp_mlp_desc* d) {
-  NgpOffsets o;
-  int64_t off = d->dense_offset;
-  int fan[kNgpLayers] = {d->enc_dim, kNgpHidden, kNgpDembDim + kNgpDensityDim, kNgpHidden, kNgpHidden};
-  for (int l = 0; l < kNgpLayers; ++l) {
-    o.w[l] = off;
-    off += (int64_t)fan[l] * ngp_out_dim(l);
-    o.b[l] = off;
-    off += ngp_out_dim(l);
-  }
-  return o;
-}
+static NgpOffsets ngp_offsets(const lnrf_ngp_mlp_desc* d) { return ngp_offsets((int)d->enc_dim, d->dense_offset); }
 // The kernels exist for NE = 1 and 2 k-steps of encoding (L*F <= 16 / <= 32): launch(integral_constant<int, NE>) -> rc
 template <class F>
 static int ngp_with_ne(const lnrf_ngp_mlp_desc* d, F&& launch) {
-  return d->enc_dim <= 16 ? launch(std::integral_constant<int, 1>{}) : launch(std::integral_constant<int, 2>{});
+  return ngp_ne((int)d->enc_dim) == 1 ? launch(Int<1>{}) : launch(Int<2>{});
 }
 #define NGP_REQUIRE_SUPPORTED(fn)                                                                          \
   if (!ngp_supported(desc)) {                                                                              \
@@ -813,11 +636,7 @@ static int64_t ngp_lmax_bytes(int64_t n_tiles) { return (n_tiles + kWaves - 1) /
 // scratch = [partial dW rows of the persistent backward] then one row of 16 per-level maxima per workgroup.  At most
 // kNgpMaxPersistent workgroups form partial rows.
 constexpr int kNgpMaxPersistent = 512;
-static int ngp_dense_params(const lnrf_ngp_mlp_desc* d) {
-  const NgpOffsets o = ngp_offsets(d);
-  return (int)(o.b[kNgpLayers - 1] + ngp_out_dim(kNgpLayers - 1) - d->dense_offset);
-}
-static int ngp_pstride(const lnrf_ngp_mlp_desc* d) { return (ngp_dense_params(d) + 63) / 64 * 64; }
+static int ngp_pstride(const lnrf_ngp_mlp_desc* d) { return (ngp_dense_params((int)d->enc_dim) + 63) / 64 * 64; }
 static int64_t ngp_lmax_off(const lnrf_ngp_mlp_desc* d, int64_t n_tiles) {
   int64_t rows = n_tiles / kWaves;
   if (rows > kNgpMaxPersistent) rows = kNgpMaxPersistent;
@@ -834,9 +653,8 @@ extern "C" int lnrf_ngp_mlp_pack(const lnrf_ngp_mlp_desc* desc, const float* par
   NGP_REQUIRE_SUPPORTED("lnrf_ngp_mlp_pack");
   LNRF_CHECK_ARG(params && packed, "null pointer");
   LNRF_CHECK_ARG(desc->dense_offset >= 0, "bad dense_offset");
-  const int ne = desc->enc_dim <= 16 ? 1 : 2;
-  hipLaunchKernelGGL(ngp_pack_kernel, dim3(64), dim3(256), 0, as_stream(stream), params, ngp_offsets(desc),
-                     (int)desc->enc_dim, ne, (char*)packed);
+  hipLaunchKernelGGL(ngp_pack_kernel<false>, dim3(64), dim3(256), 0, as_stream(stream), params, ngp_offsets(desc),
+                     (int)desc->enc_dim, ngp_ne((int)desc->enc_dim), (char*)packed);
   LNRF_LAUNCH_CHECK();
   return LNRF_OK;
 }
@@ -850,9 +668,8 @@ extern "C" int lnrf_ngp_mlp_pack_split(const lnrf_ngp_mlp_desc* desc, const floa
   NGP_REQUIRE_SUPPORTED("lnrf_ngp_mlp_pack_split");
   LNRF_CHECK_ARG(params && packed_split, "null pointer");
   LNRF_CHECK_ARG(desc->dense_offset >= 0, "bad dense_offset");
-  const int ne = desc->enc_dim <= 16 ? 1 : 2;
-  hipLaunchKernelGGL(ngp_pack_split_kernel, dim3(64), dim3(256), 0, as_stream(stream), params, ngp_offsets(desc),
-                     (int)desc->enc_dim, ne, (char*)packed_split);
+  hipLaunchKernelGGL(ngp_pack_kernel<true>, dim3(64), dim3(256), 0, as_stream(stream), params, ngp_offsets(desc),
+                     (int)desc->enc_dim, ngp_ne((int)desc->enc_dim), (char*)packed_split);
   LNRF_LAUNCH_CHECK();
   return LNRF_OK;
 }
@@ -894,7 +711,7 @@ extern "C" int lnrf_ngp_mlp_fwd(const lnrf_ngp_mlp_desc* desc, const void* packe
     constexpr int NE = decltype(ne_)::value;
     if (int rc = set_max_dynamic_lds(ngp_mlp_kernel<NE, false>, kNgpLds)) return rc;
     hipLaunchKernelGGL((ngp_mlp_kernel<NE, false>), grid, block, kNgpLds, st, (const char*)packed, enc_t, d,
-                       (int)desc->enc_dim, m, n_tiles, density, rgb, nullptr, nullptr, nullptr, nullptr);
+                       (int)desc->enc_dim, m, n_tiles, density, rgb, nullptr, nullptr, nullptr);
     return (int)LNRF_OK;
   });
   if (rc) return rc;
@@ -919,22 +736,7 @@ extern "C" int lnrf_ngp_mlp_bwd(const lnrf_ngp_mlp_desc* desc, const void* packe
   const int n_levels = desc->enc_dim / 2;
   // weight-gradient problems (five Dense layers): where each kernel's rows and columns sit in the gradient vector
   const NgpOffsets off = ngp_offsets(desc);
-  const int lf = desc->enc_dim;
-  NgpWgradArgs a;
-  auto add = [&](int i, int layer, int rb0, int rv0, int rb1, int rv1, int rb2, int rv2, int rb3, int rv3) {
-    NgpWgradProblem p{};
-    p.out_dim = ngp_out_dim(layer);
-    p.w_lo = (unsigned)(off.w[layer] & 0xFFFFFFFFll); p.w_hi = (unsigned)(off.w[layer] >> 32);
-    p.b_lo = (unsigned)(off.b[layer] & 0xFFFFFFFFll); p.b_hi = (unsigned)(off.b[layer] >> 32);
-    p.rb0 = rb0; p.rv0 = rv0; p.rb1 = rb1; p.rv1 = rv1;
-    p.rb2 = rb2; p.rv2 = rv2; p.rb3 = rb3; p.rv3 = rv3;
-    a.p[i] = p;
-  };
-  add(0, 3, 0, 16, 16, 16, 32, 16, 48, 16);
-  add(1, 2, 0, 16, 16, 8, kNgpDembDim, 16, 0, 0);
-  add(2, 1, 0, 16, 16, 16, 32, 16, 48, 16);
-  add(3, 4, 0, 16, 16, 16, 32, 16, 48, 16);
-  add(4, 0, 0, lf < 16 ? lf : 16, 16, lf > 16 ? lf - 16 : 0, 0, 0, 0, 0);
+  const NgpWgradArgs a = ngp_wgrad_args(off, desc->enc_dim);
   // one persistent workgroup per CU forms the weight gradients itself (no dumps, no second launch)
   int cus = 0;
   if (int rc = cu_count(&cus)) return rc;
@@ -943,21 +745,15 @@ extern "C" int lnrf_ngp_mlp_bwd(const lnrf_ngp_mlp_desc* desc, const void* packe
   if (nb > kNgpMaxPersistent) nb = kNgpMaxPersistent;
   const dim3 pgrid((unsigned)nb), block(kThreads);
   // partial dW rows (workgroup, k-part) at the front of the scratch buffer
-  NgpPartsPlan plan;
-  for (int i = 0; i < kNgpLayers; ++i) {
-    const int layer = i == 0 ? 3 : (i == 1 ? 2 : (i == 2 ? 1 : (i == 3 ? 4 : 0)));  // problem i of the table above
-    plan.lo[i] = (int)(off.w[layer] - desc->dense_offset);
-    plan.hi[i] = (int)(off.b[layer] - desc->dense_offset) + ngp_out_dim(layer);
-    plan.parts[i] = ngp_wgrad_parts(i);
-  }
-  const int n_params = ngp_dense_params(desc);
+  const NgpPartsPlan plan = ngp_parts_plan(off, desc->dense_offset);
+  const int n_params = ngp_dense_params((int)desc->enc_dim);
   const int pstride = ngp_pstride(desc);
   float* wparts = reinterpret_cast<float*>(scratch);
   const int rc = ngp_with_ne(desc, [&](auto ne_) {
     constexpr int NE = decltype(ne_)::value;
     if (int rc = set_max_dynamic_lds(ngp_mlp_kernel<NE, true>, kNgpFusedLds)) return rc;
     hipLaunchKernelGGL((ngp_mlp_kernel<NE, true>), pgrid, block, kNgpFusedLds, st, (const char*)packed, enc_t, d,
-                       (int)desc->enc_dim, m, n_tiles, nullptr, nullptr, g_density, g_rgb, nullptr, g_enc_t,
+                       (int)desc->enc_dim, m, n_tiles, nullptr, nullptr, g_density, g_rgb, g_enc_t,
                        lmax_parts, a, wparts, pstride, (int64_t)desc->dense_offset);
     return (int)LNRF_OK;
   });

@@ -21,11 +21,6 @@ namespace lnrf {
 
 constexpr int kRefLds = kRingBytes + round_up(kBiasFloats * 4, 1024);
 
-template <int COUNT>
-struct LinSeq {  // a stream consumed front to back without padding
-  static constexpr int count = COUNT;
-  static constexpr int at(int c) { return c; }
-};
 template <int LAYERS>
 struct FwdPrefixSeq {  // the forward stream up to (not including) stream layer LAYERS
   static constexpr int count = fwd_cons_base(LAYERS);

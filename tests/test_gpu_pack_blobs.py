@@ -4,6 +4,7 @@ layout library (csrc/nerf_layout.h pack walks, exported by liblnrf_layout_host.s
 kernel writes, no tolerance.  Weights are bf16(params[idx]) with 0 for idx == -1, split streams hold hi = bf16(w) in the even
 and lo = bf16(w - float(hi)) in the odd fragments, biases are exact fp32; the region offsets are the library's constants.
 The unwritten tail behind a bias block is not compared.
+The two InstantNGPModel pack kernels likewise, against the index arrays of csrc/ngp_layout.h (test_ngp_layout.py).
 """
 import ctypes
 
@@ -13,6 +14,7 @@ import torch
 
 from learn_nerf import _lib as L
 from test_nerf_layout import HOST_LIB, stream_indices
+from test_ngp_layout import dense_layout, ngp_stream_indices
 
 pytestmark = pytest.mark.gpu
 
@@ -23,6 +25,9 @@ N_PARAMS = 593_924  # NeRFModel; RefNERFModel's vector is shorter
 def H():
     lib = ctypes.CDLL(HOST_LIB)
     lib.lnrf_host_pack_offset.restype = ctypes.c_int64
+    lib.lnrf_host_ngp_pack_offset.restype = ctypes.c_int64
+    lib.lnrf_host_ngp_stream_indices.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_void_p]
+    lib.lnrf_host_ngp_stream_indices.restype = ctypes.c_int64
     return lib
 
 
@@ -123,3 +128,42 @@ def test_refnerf_render_pack(H, params):
                         ("split normal pass", O(13), split_bytes(params, stream_indices(H, "nrm"), True)),
                         ("split directional forward", O(14), split_bytes(params, stream_indices(H, "dir_fwd"), True)),
                         ("directional bias", O(15), f32_bytes(params, stream_indices(H, "dir_bias")))], n)
+
+
+def run_ngp_pack(fn_name, bytes_fn_name, params, enc_dim, dense_offset):
+    lib = L.lib()
+    desc = L.NgpMlpDesc(enc_dim, 64, 16, 1, 2, 4, dense_offset)
+    nbytes = getattr(lib, bytes_fn_name)(ctypes.byref(desc))
+    flat = params[:dense_offset + dense_layout(enc_dim)[1]].cuda()
+    packed = torch.full((nbytes,), 0xA5, dtype=torch.uint8, device="cuda")
+    L.check(getattr(lib, fn_name)(ctypes.byref(desc), L.ptr(flat), L.ptr(packed, torch.uint8), L.stream()), fn_name)
+    torch.cuda.synchronize()
+    return packed.cpu(), nbytes
+
+
+def ngp_indices(H, stream, enc_dim, dense_offset):
+    idx = ngp_stream_indices(H, stream, enc_dim).astype(np.int64)  # relative to the first Dense parameter
+    return np.where(idx >= 0, idx + dense_offset, -1)
+
+
+@pytest.mark.parametrize("dense_offset", [0, 1001])
+@pytest.mark.parametrize("enc_dim", [1, 6, 16, 17, 32])
+def test_ngp_mlp_pack(H, params, enc_dim, dense_offset):
+    O = H.lnrf_host_ngp_pack_offset
+    got, n = run_ngp_pack("lnrf_ngp_mlp_pack", "lnrf_ngp_mlp_packed_bytes", params, enc_dim, dense_offset)
+    assert n == O(1)
+    # one stream of 48 fragments: the forward walk owns the front, the transposed walk what follows (never both)
+    stream = np.maximum(ngp_indices(H, 0, enc_dim, dense_offset), ngp_indices(H, 1, enc_dim, dense_offset))
+    check_regions(got, [("stream", 0, bf16_bytes(params, stream)),
+                        ("bias", O(0), f32_bytes(params, ngp_indices(H, 2, enc_dim, dense_offset)))], n)
+
+
+@pytest.mark.parametrize("dense_offset", [0, 1001])
+@pytest.mark.parametrize("enc_dim", [1, 6, 16, 17, 32])
+def test_ngp_mlp_pack_split(H, params, enc_dim, dense_offset):
+    O = H.lnrf_host_ngp_pack_offset
+    got, n = run_ngp_pack("lnrf_ngp_mlp_pack_split", "lnrf_ngp_mlp_packed_split_bytes", params, enc_dim, dense_offset)
+    assert n == O(3)
+    fwd = ngp_indices(H, 0, enc_dim, dense_offset)[:O(5) * 512]  # the blob pairs the first 26 fragments
+    check_regions(got, [("split forward", 0, split_bytes(params, fwd, True)),
+                        ("bias", O(2), f32_bytes(params, ngp_indices(H, 2, enc_dim, dense_offset)))], n)
