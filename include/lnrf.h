@@ -194,7 +194,14 @@ int lnrf_dense_bwd_weight_det(const float* x, int64_t ldx, const float* gy, int6
  *   C[i*ldc + j] (op)= sum_r A[i*sa_i + r*sa_r] * B[r*sb_r + j*sb_j],  i < I, j < J, r < R
  * mode 0: C = act(sum + bias[j]);  1: C += sum;  2: atomic C += sum with the reduction split over
  * `splits` workgroups (0 = choose).  Lets a layer consume a transposed operand (e.g. the feature-major
- * hash-grid encoding) without a copy. */
+ * hash-grid encoding) without a copy.
+ * Any strides and any 4-byte-aligned pointers are accepted: strides and alignment only select the kernel
+ * (csrc/dense_plan.h), and every kernel gives the same result to within the rounding of an fp32 sum,
+ *   |C - C_exact| <= (R + splits + 2) 2^-23 (|A| |B|)_ij + 2^-23 |C_exact|
+ * (C_exact: the product of the operands as multiplied, i.e. rounded to bf16 under LNRF_DENSE_BF16).  Nothing outside
+ * the I x J elements of C is written, and nothing outside the I x R elements of A and the R x J elements of B (rows
+ * and columns beyond the extents, the padding between rows, elements skipped by a stride) influences the result.
+ * tests/test_gpu_gemm_paths.py pins this for every kernel the plan can select. */
 int lnrf_gemm_f32(const float* a, int64_t sa_i, int64_t sa_r, const float* b, int64_t sb_r, int64_t sb_j,
                   float* c, int64_t ldc, const float* bias, int32_t act, int32_t mode, int64_t i_rows,
                   int32_t j_cols, int64_t r_depth, int32_t splits, lnrf_stream_t stream);

@@ -7,6 +7,7 @@
 #include <utility>
 
 #include "common.h"
+#include "dense_plan.h"
 
 namespace lnrf {
 
@@ -39,8 +40,6 @@ __device__ __forceinline__ float act_grad_from_output(float y, int act) {
     default: return 1.0f;
   }
 }
-
-constexpr int TI = 64, TJ = 64, RC = 16;
 
 // Optional epilogue gate: C(i, j) *= act'(gate[i][j]) for j < n (activation derivative through its OUTPUT), i.e. the
 // activation backward of the layer below fused into the GEMM that produces its input gradient (one pass over a
@@ -175,7 +174,6 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(const float* __restrict__
 // B_FAST_R: B(r, j) contiguous in r (W^T of the input gradient) else in j (W, dy).  The generic kernel above
 // spends ~15 instructions per operand element on address arithmetic and scalar staging, which caps it at
 // ~60 (f32) / ~100 (bf16) TFLOP/s; this one moves 4 elements per load.
-constexpr int BI = 128, BJ = 128;
 // bf16 LDS image of an operand tile: [row][k] with the 16-byte chunks (8 k) of a row XOR-swizzled by bits 2..3 of the
 // row.  The operand that is contiguous along its row dimension in memory arrives as float4 = 4 ROWS at one k, i.e.
 // as scalar 2-byte LDS stores 4 rows apart: without the swizzle they fall on 4 banks (8-way conflict).
@@ -187,7 +185,7 @@ __global__ __launch_bounds__(256) void gemm_big_kernel(const float* __restrict__
                                                        float* __restrict__ c, int64_t ldc,
                                                        const float* __restrict__ bias, int act, int mode, int64_t I,
                                                        int J, int64_t R, int64_t r_per_split, Gate gate) {
-  constexpr int KC = BF16 ? 32 : 16;                 // reduction depth per chunk
+  constexpr int KC = BF16 ? kBigKcBf16 : kBigKcF32;  // reduction depth per chunk
   constexpr int NV = (BI * KC / 4) / 256;            // float4 per thread and operand
   __shared__ __attribute__((aligned(16))) __bf16 Ah[BF16 ? BI : 1][KC + 8];
   __shared__ __attribute__((aligned(16))) __bf16 Bh[BF16 ? BJ : 1][KC + 8];
@@ -196,22 +194,11 @@ __global__ __launch_bounds__(256) void gemm_big_kernel(const float* __restrict__
   const int tid = threadIdx.x;
   const int lane = tid & 63, wave = tid >> 6;
   const int wr = wave >> 1, wc = wave & 1;
-  // XCD-aware tile order: workgroups are dealt round-robin over the 8 XCDs (blocks b and b + 8 share an L2), so
-  // the column tiles of one row tile are placed 8 blocks apart: the second one finds the A tile in its XCD's L2
-  // instead of re-reading it from HBM.  blockIdx.x = (8 nj) g + 8 jt + t  ->  row tile 8 g + t, column tile jt.
-  // (Few row tiles, e.g. the split-K weight gradient: plain order, or all the work would land on ni of the 8 XCDs.)
   const int nj = (J + BJ - 1) / BJ;
   const int64_t ni = (I + BI - 1) / BI;
-  int64_t it;
-  int jt;
-  if (ni >= 64) {
-    const unsigned grp = blockIdx.x / (8u * nj), rem = blockIdx.x % (8u * nj);
-    it = (int64_t)grp * 8 + (rem & 7u);
-    jt = (int)(rem >> 3);
-  } else {
-    it = blockIdx.x % (unsigned)ni;
-    jt = (int)(blockIdx.x / (unsigned)ni);
-  }
+  const GemmTile tile = gemm_big_tile(blockIdx.x, ni, nj);  // XCD-aware tile order: dense_plan.h
+  const int64_t it = tile.it;
+  const int jt = tile.jt;
   const int64_t i0 = it * BI;
   if (i0 >= I || jt >= nj) return;
   const int j0 = jt * BJ;
@@ -373,8 +360,6 @@ __global__ __launch_bounds__(256) void gemm_big_kernel(const float* __restrict__
   }
 }
 
-constexpr int kColSumRows = 512;
-
 // out[e] += parts[0][e] + parts[1][e] + ... in that order (e < count): the deterministic end of a split reduction
 __global__ __launch_bounds__(256) void dense_fold_kernel(const float* __restrict__ parts, int n_parts, int64_t count,
                                                          float* __restrict__ out) {
@@ -437,46 +422,29 @@ __global__ void sinusoidal_emb_kernel(const float* __restrict__ x, int64_t ldx, 
 
 using namespace lnrf;
 
-static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+static inline unsigned low_bits(const void* p) { return (unsigned)(reinterpret_cast<uintptr_t>(p) & 15u); }
 
+// Launches what gemm_plan (dense_plan.h) decides.  mode 3 = split partials (see gemm_f32_kernel).
 static int launch_gemm(const float* a, int64_t sa_i, int64_t sa_r, const float* b, int64_t sb_r,
                        int64_t sb_j, float* c, int64_t ldc, const float* bias, int act, int mode,
                        int64_t I, int J, int64_t R, int splits, hipStream_t stream,
                        Gate gate = Gate{nullptr, 0, 0, 0}, int* splits_used = nullptr) {
-  if (splits_used) *splits_used = 0;
-  if (I == 0 || J == 0) return LNRF_OK;
-  if (splits < 1) splits = 1;
-  // vectorised 128x128 kernel: both operands contiguous along one of their dimensions, 16-byte aligned rows,
-  // extents along the contiguous dimensions multiples of 4, and enough work to fill 128-wide tiles
-  const bool a_fast_r = sa_r == 1, a_fast_i = sa_i == 1 && !a_fast_r;
-  const bool b_fast_r = sb_r == 1, b_fast_j = sb_j == 1;
-  const int64_t lda = a_fast_r ? sa_i : sa_r, ldb = b_fast_r ? sb_j : sb_r;
-  // A contiguous in i = X^T of the weight gradient: transposing LDS stores (swizzled bf16 image / 17-float rows in f32)
-  const bool b_al = aligned16(b);  // weights inside a flat parameter vector may start at any float
-  const bool big = (a_fast_r || a_fast_i) && (b_fast_r || b_fast_j) && aligned16(a) &&
-                   lda % 4 == 0 && ldb % 4 == 0 && (a_fast_r ? R % 4 == 0 : I % 4 == 0) &&
-                   (b_fast_r ? R % 4 == 0 : J % 4 == 0) && I >= 64 && J >= 64 && R >= 32;
-  if (big) {
-    const int kc = g_dense_bf16 ? 32 : 16;
-    int64_t per = (R + splits - 1) / splits;
-    per = ((per + kc - 1) / kc) * kc;
-    if (per % 4 != 0) per = ((per + 3) / 4) * 4;
-    int nsplit = (int)((R + per - 1) / per);
-    if (nsplit < 1) nsplit = 1;
-    if (splits_used) *splits_used = nsplit;
-    const int64_t ni = (I + BI - 1) / BI, njt = (J + BJ - 1) / BJ;
-    dim3 grid((unsigned)((ni >= 64 ? ((ni + 7) / 8) * 8 : ni) * njt), 1u, (unsigned)nsplit);  // tile order: see the kernel
+  const GemmPlan p = gemm_plan(sa_i, sa_r, sb_r, sb_j, I, J, R, low_bits(a), low_bits(b), g_dense_bf16 != 0, mode, splits);
+  if (splits_used) *splits_used = p.nsplit;
+  if (!p.launch) return LNRF_OK;
+  const dim3 grid(p.gx, p.gy, p.gz);
+  if (p.big) {
 #define LNRF_BIG(BF, AR, BR)                                                                                          \
   do {                                                                                                                \
-    if (b_al)                                                                                                         \
-      hipLaunchKernelGGL((gemm_big_kernel<BF, AR, BR, true>), grid, dim3(256), 0, stream, a, lda, b, ldb, c, ldc, bias, \
-                         act, mode, I, J, R, per, gate);                                                              \
+    if (p.b_aligned)                                                                                                  \
+      hipLaunchKernelGGL((gemm_big_kernel<BF, AR, BR, true>), grid, dim3(256), 0, stream, a, p.lda, b, p.ldb, c, ldc, \
+                         bias, act, mode, I, J, R, p.r_per_split, gate);                                              \
     else                                                                                                              \
-      hipLaunchKernelGGL((gemm_big_kernel<BF, AR, BR, false>), grid, dim3(256), 0, stream, a, lda, b, ldb, c, ldc,    \
-                         bias, act, mode, I, J, R, per, gate);                                                        \
+      hipLaunchKernelGGL((gemm_big_kernel<BF, AR, BR, false>), grid, dim3(256), 0, stream, a, p.lda, b, p.ldb, c, ldc, \
+                         bias, act, mode, I, J, R, p.r_per_split, gate);                                              \
   } while (0)
-    const bool ar = a_fast_r, br = !b_fast_j;
-    if (g_dense_bf16) {
+    const bool ar = p.a_fast_r, br = p.b_fast_r;
+    if (p.bf16) {
       if (ar && br) LNRF_BIG(true, true, true); else if (ar) LNRF_BIG(true, true, false);
       else if (br) LNRF_BIG(true, false, true); else LNRF_BIG(true, false, false);
     } else {
@@ -488,19 +456,12 @@ static int launch_gemm(const float* a, int64_t sa_i, int64_t sa_r, const float* 
     if (e != hipSuccess) return hip_fail(e, "gemm_big");
     return LNRF_OK;
   }
-  int64_t per = (R + splits - 1) / splits;
-  per = ((per + RC - 1) / RC) * RC;
-  if (per < RC) per = RC;
-  splits = (int)((R + per - 1) / per);
-  if (splits < 1) splits = 1;
-  if (splits_used) *splits_used = splits;
-  dim3 grid((unsigned)((I + TI - 1) / TI), (unsigned)((J + TJ - 1) / TJ), (unsigned)splits);
-  if (g_dense_bf16)
+  if (p.bf16)
     hipLaunchKernelGGL(gemm_f32_kernel<true>, grid, dim3(256), 0, stream, a, sa_i, sa_r, b, sb_r, sb_j, c, ldc,
-                       bias, act, mode, I, J, R, per, gate);
+                       bias, act, mode, I, J, R, p.r_per_split, gate);
   else
     hipLaunchKernelGGL(gemm_f32_kernel<false>, grid, dim3(256), 0, stream, a, sa_i, sa_r, b, sb_r, sb_j, c, ldc,
-                       bias, act, mode, I, J, R, per, gate);
+                       bias, act, mode, I, J, R, p.r_per_split, gate);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return hip_fail(e, "gemm_f32");
   return LNRF_OK;
@@ -565,19 +526,10 @@ extern "C" int lnrf_dense_fwd_gated(const float* x, int64_t ldx, const float* w,
   return launch_gemm(x, ldx, 1, w, n, 1, y, ldy, b, act, 0, m, n, k, 1, as_stream(stream), Gate{y_gate, ldg, act_gate, n});
 }
 
-static int wgrad_splits(int64_t m, int k, int n) {
-  const int tiles = ((k + TI - 1) / TI) * ((n + TJ - 1) / TJ);
-  int splits = (int)((2048 + tiles - 1) / tiles);
-  if (splits > 512) splits = 512;
-  const int64_t max_splits = (m + 255) / 256;
-  if (splits > max_splits) splits = (int)max_splits;
-  return splits < 1 ? 1 : splits;
-}
+// split count of the weight gradient's reduction over m: what the scratch is sized for and what launch_gemm is asked for
+static int wgrad_splits(int64_t m, int k, int n) { return gemm_auto_splits(k, n, m); }
 extern "C" int64_t lnrf_dense_bwd_weight_scratch_bytes(int64_t m, int32_t k, int32_t n) {
-  if (m < 0 || k < 0 || n < 1) return -1;
-  const int64_t kernel_parts = k > 0 ? (int64_t)wgrad_splits(m, k, n) * k * n : 0;
-  const int64_t bias_parts = (m + kColSumRows - 1) / kColSumRows * n;
-  return (kernel_parts + bias_parts) * (int64_t)sizeof(float) + 256;
+  return dense_wgrad_scratch_bytes(m, k, n);
 }
 
 // Weight and bias gradients of a Dense layer, gw[k][n] += x^T gy and gb[n] += column sums of gy (x == gw == nullptr: bias
@@ -634,31 +586,16 @@ extern "C" int lnrf_gemm_f32(const float* a, int64_t sa_i, int64_t sa_r, const f
   LNRF_CHECK_ARG(a && b && c, "null pointer");
   LNRF_CHECK_ARG(i_rows >= 0 && j_cols >= 0 && r_depth >= 1 && ldc >= j_cols, "bad sizes");
   LNRF_CHECK_ARG(mode >= 0 && mode <= 2 && act >= 0 && act <= LNRF_ACT_SIGMOID, "bad mode/activation");
-  if (mode != 2) splits = 1;
-  if (mode == 2 && splits <= 0) {
-    const int64_t tiles = ((i_rows + TI - 1) / TI) * ((j_cols + TJ - 1) / TJ);
-    splits = (int)((2048 + tiles - 1) / (tiles > 0 ? tiles : 1));
-    if (splits > 512) splits = 512;
-    const int64_t max_splits = (r_depth + 255) / 256;
-    if (splits > max_splits) splits = (int)max_splits;
-  }
+  // gemm_plan: modes 0 and 1 never split, mode 2 with splits <= 0 chooses (gemm_auto_splits)
   return launch_gemm(a, sa_i, sa_r, b, sb_r, sb_j, c, ldc, bias, act, mode, i_rows, j_cols, r_depth, splits,
                      as_stream(stream));
 }
 
 // lnrf_gemm_f32 mode 2 with a fixed summation order: C (contiguous rows, ldc == J) += sum over r, the splits of the
 // reduction leaving their partial tiles in `scratch` (lnrf_gemm_f32_det_scratch_bytes) and added in order.
-static int gemm_det_splits(int64_t I, int J, int64_t R) {
-  const int64_t tiles = ((I + TI - 1) / TI) * ((J + TJ - 1) / TJ);
-  int64_t splits = (2048 + tiles - 1) / (tiles > 0 ? tiles : 1);
-  if (splits > 512) splits = 512;
-  const int64_t max_splits = (R + 255) / 256;
-  if (splits > max_splits) splits = max_splits;
-  return splits < 1 ? 1 : (int)splits;
-}
+static int gemm_det_splits(int64_t I, int J, int64_t R) { return gemm_auto_splits(I, J, R); }
 extern "C" int64_t lnrf_gemm_f32_det_scratch_bytes(int64_t i_rows, int32_t j_cols, int64_t r_depth) {
-  if (i_rows < 0 || j_cols < 0 || r_depth < 0) return -1;
-  return (int64_t)gemm_det_splits(i_rows, j_cols, r_depth) * i_rows * j_cols * (int64_t)sizeof(float) + 256;
+  return gemm_det_scratch_bytes(i_rows, j_cols, r_depth);
 }
 extern "C" int lnrf_gemm_f32_det(const float* a, int64_t sa_i, int64_t sa_r, const float* b, int64_t sb_r, int64_t sb_j,
                                  float* c, int64_t i_rows, int32_t j_cols, int64_t r_depth, void* scratch,

@@ -1,9 +1,11 @@
 // layout_host.cpp — host build of the index maps of the fused NeRF kernels (nerf_layout.h) and of the
 // positional-encoding sincos (fast_math.h), so that tests/test_nerf_layout.py can run the exact packing /
 // fragment logic on the CPU (no GPU needed) with an MFMA emulator; and of the weight-gradient problem lists and their
-// gradient-vector addressing (nerf_wgrad.h); and of the tables and pack walks of the fused InstantNGPModel MLP (ngp_layout.h).
+// gradient-vector addressing (nerf_wgrad.h); and of the tables and pack walks of the fused InstantNGPModel MLP (ngp_layout.h);
+// and of the dispatch plan and tile map of the generic dense GEMM (dense_plan.h, tests/test_dense_plan.py).
 #include <stdint.h>
 
+#include "dense_plan.h"
 #include "fast_math.h"
 #include "nerf_wgrad.h"
 #include "ngp_layout.h"
@@ -225,6 +227,27 @@ int lnrf_host_ngp_parts_plan(int enc_dim, int32_t* out) {
   }
   return ngp_dense_params(enc_dim);
 }
+// ---- generic dense GEMM (dense_plan.h): the plan launch_gemm launches from.  out[0..14] = launch, big, bf16, a_fast_r,
+// b_fast_r, b_aligned, kc, nsplit, lda, ldb, r_per_split, grid x / y / z, and GemmPlan::splits
+void lnrf_host_gemm_plan(int64_t sa_i, int64_t sa_r, int64_t sb_r, int64_t sb_j, int64_t I, int32_t J, int64_t R,
+                         uint32_t a_low, uint32_t b_low, int32_t bf16, int32_t mode, int32_t splits, int64_t* out) {
+  const GemmPlan p = gemm_plan(sa_i, sa_r, sb_r, sb_j, I, J, R, a_low, b_low, bf16 != 0, mode, splits);
+  const int64_t v[15] = {p.launch, p.big, p.bf16, p.a_fast_r, p.b_fast_r, p.b_aligned, p.kc, p.nsplit, p.lda, p.ldb,
+                         p.r_per_split, p.gx, p.gy, p.gz, p.splits};
+  for (int i = 0; i < 15; ++i) out[i] = v[i];
+}
+// tiles of blocks block0 .. block0 + count - 1 of gemm_big_kernel's grid for an I x J output: out[2 e] = row tile,
+// out[2 e + 1] = column tile of block block0 + e
+void lnrf_host_gemm_tile(int64_t I, int32_t J, uint32_t block0, int64_t count, int64_t* out) {
+  for (int64_t e = 0; e < count; ++e) {
+    const GemmTile t = gemm_big_tile(block0 + (uint32_t)e, (I + BI - 1) / BI, (J + BJ - 1) / BJ);
+    out[2 * e] = t.it;
+    out[2 * e + 1] = t.jt;
+  }
+}
+// the scratch sizes behind lnrf_dense_bwd_weight_scratch_bytes / lnrf_gemm_f32_det_scratch_bytes
+int64_t lnrf_host_dense_bwd_weight_scratch_bytes(int64_t m, int32_t k, int32_t n) { return dense_wgrad_scratch_bytes(m, k, n); }
+int64_t lnrf_host_gemm_det_scratch_bytes(int64_t I, int32_t J, int64_t R) { return gemm_det_scratch_bytes(I, J, R); }
 int64_t lnrf_host_wgrad_owners(int which, int64_t n_tiles, int32_t* count, int64_t n) {
   const WgradList list = wgrad_list_of(which, n_tiles);
   int64_t outside = 0;
