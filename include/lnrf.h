@@ -417,8 +417,8 @@ int lnrf_nerf_mlp_bwd_ls2(const lnrf_nerf_shape* shape, const void* packed_a, co
  *                               u = d L / d n_raw [m, 3] (jax.grad of a function that calls jax.grad, train.py:89-90
  *                               over ref_nerf.py:42; scratch: lnrf_nerf_save_bytes; the slab region behind the chain
  *                               states in cdump is used as workspace for the fixed-order weight-gradient fold)
- * Head, integrated directional encoding and the 273 -> 128 -> 3 directional block: lnrf_refnerf_head_*,
- * lnrf_refnerf_color_*, lnrf_dense_*. */
+ * Head and integrated directional encoding: lnrf_refnerf_head_*, lnrf_refnerf_color_*.  The 273 -> 128 -> 3 directional
+ * block is fused as well: lnrf_refnerf_dir_* below (its streams are part of the same packed blob). */
 int64_t lnrf_refnerf_trunk_packed_bytes(void);
 int lnrf_refnerf_trunk_pack(const float* params, void* packed, lnrf_stream_t stream);
 int lnrf_refnerf_trunk_fwd(const void* packed, const float* x, int64_t m, void* save, float* spatial_out,
@@ -435,7 +435,10 @@ int lnrf_refnerf_normal_bwd(const void* packed, const void* save, const void* cd
  *   lnrf_refnerf_dir_fwd   dir_out[m, 3] (pre-sigmoid) from dir_in[m, 0:273] = [spatial_out, IDE, -d.n] (fp32, `ld` >=
  *                          276 floats per row, rows 16-byte aligned); dsave: lnrf_refnerf_dir_save_bytes(m)
  *   lnrf_refnerf_dir_bwd   g_dir_in[m, 0:273] = d L / d dir_in (overwritten) and grads += d L / d Dense_9, Dense_10 given
- *                          g_dir_out[m, 3]; scratch: lnrf_refnerf_dir_scratch_bytes(m) */
+ *                          g_dir_out[m, 3]; scratch: lnrf_refnerf_dir_scratch_bytes(m).  g_dir_in has `ld` floats per row
+ *                          (>= 276, a multiple of 4, rows 16-byte aligned); of each of the m rows, columns
+ *                          273 .. min(ld, 288) - 1 receive 0, nothing at or beyond column 288 is touched.
+ * Neither call reads columns 273 .. ld - 1 of dir_in. */
 int64_t lnrf_refnerf_dir_save_bytes(int64_t m);
 int64_t lnrf_refnerf_dir_scratch_bytes(int64_t m);
 int lnrf_refnerf_dir_fwd(const void* packed, const float* dir_in, int64_t ld, int64_t m, void* dsave,

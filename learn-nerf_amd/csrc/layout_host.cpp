@@ -142,6 +142,12 @@ int lnrf_host_save_slot(int what, int arg) {
 int lnrf_host_grad_slot(int what, int arg) {
   return what == 0 ? kGradDy11 : what == 1 ? kGradDy10m : what == 2 ? grad_dy_slot(arg) : kGradSlots;
 }
+// Ref-NeRF directional block: what 0 input fragments, 1 relu(Dense_9), 2 its mask, 3 slots per tile of the save | 4 dy10,
+// 5 dy9, 6 slots per tile of the gradient dump; -1 for anything else
+int lnrf_host_dir_slot(int what) {
+  const int v[7] = {kDirSaveXin, kDirSaveH, kDirSaveMask, kDirSaveSlots, kDirGradDy10, kDirGradDy9, kDirGradSlots};
+  return what >= 0 && what < 7 ? v[what] : -1;
+}
 int lnrf_host_demb_feat(int ks, int h, int j) { return demb_feat(ks, h, j); }
 int lnrf_host_hidden_feat(int ks, int h, int j) { return hidden_feat(ks, h, j); }
 // what 0 bytes per fragment, 1 evaluations per tile, 2 tiles per workgroup (dumps are padded to whole workgroups)

@@ -12,8 +12,12 @@ k-slot <-> feature map is read from liblnrf_layout_host.so (csrc/nerf_layout.h c
 tensor widths only.  The maps of dy11 and dy10m come from the transposed weight stream itself: k-slot (h, j) of k-step ks
 carries the output feature whose weight bwd_weight_index() puts there.
 
-A dump is described by a list of TensorMap (bf16 tensors) and MaskMap (ReLU-mask slots); the Ref-NeRF directional dumps
-(kDirSave*, kDirGrad*) can be added as two more lists.
+A dump is described by a list of TensorMap (bf16 tensors) and MaskMap (ReLU-mask slots).  The Ref-NeRF directional block
+(lnrf_refnerf_dir_fwd / _dir_bwd, csrc/refnerf_fused.hip) leaves two more dumps of the same form, dir_layouts():
+
+  directional save           xin (the 273 inputs as bf16, 18 k-steps, k-slots 273..287 zero), h9 = relu(Dense_9) (8), mask9
+  directional gradient dump  front of the scratch of lnrf_refnerf_dir_bwd: dy10 (2 slots, the second all zero; k-slot map
+                             from the Dense_10^T rows of the transposed directional stream), dy9 (8)
 """
 import ctypes
 import functools
@@ -29,6 +33,7 @@ HOST_LIB = os.path.join(ROOT, "learn-nerf_amd", "lib", "liblnrf_layout_host.so")
 X_EMB, D_EMB, HIDDEN, COLOR = 60, 24, 256, 128
 DENSE_DIMS = [(X_EMB, HIDDEN)] + [(HIDDEN, HIDDEN)] * 4 + [(HIDDEN + X_EMB, HIDDEN)] + [(HIDDEN, HIDDEN)] * 3 + \
              [(HIDDEN, 1), (HIDDEN + D_EMB, COLOR), (COLOR, 3)]
+DIR_IN, DIR_HIDDEN = 273, 128  # RefNERFModel's directional block: Dense_9 273 -> 128 relu, Dense_10 128 -> 3
 U23 = 2.0 ** -23  # unit roundoff of a chopping fp32 accumulator; also covers round-to-nearest (2^-24)
 
 
@@ -345,6 +350,103 @@ def encode_grad(t, m):
     for name, val in named.items():
         lay.write(blocks, name, _rows(val, n_tiles * lay.cols, lay.tensors[name].width))
     return blocks.reshape(-1)
+
+
+# ---- Ref-NeRF directional block -----------------------------------------------------------------------------------------
+def _dir_dy10_feat(lib, n_slots):
+    """k-slot -> colour channel map of dy10, read off the Dense_10^T rows of the transposed directional stream (as
+    _stream_feat does for dy11): k-slot (h, j) of its one k-step carries the channel whose weight of hidden feature 0 the
+    pack walk puts in A row 0 of out tile 0.  The slots behind the first carry nothing."""
+    lib.lnrf_host_stream_indices.restype = ctypes.c_int64
+    lib.lnrf_host_stream_indices.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_void_p]
+    n = lib.lnrf_host_stream_indices(6, 0, None)
+    idx = np.empty(n, np.int32)
+    assert lib.lnrf_host_stream_indices(6, 0, idx.ctypes.data) == n
+    idx = idx.reshape(-1, 64, 8)
+    w10, b10 = lib.lnrf_host_wgrad_const(6), lib.lnrf_host_wgrad_const(7)
+    feat = np.full((n_slots, 2, 8), -1, np.int64)
+    for h in range(2):
+        for j in range(8):
+            i = int(idx[0, lib.lnrf_host_dump_info(1) * h, j])
+            if i >= 0:
+                assert w10 <= i < b10 and (i - w10) // 3 == 0, (h, j, i)
+                feat[0, h, j] = (i - w10) % 3
+    return feat
+
+
+@functools.lru_cache(maxsize=None)
+def dir_layouts():
+    """-> (directional save layout, directional gradient-dump layout), from the host layout library"""
+    lib = load_host_lib()
+    S = lib.lnrf_host_dir_slot
+    nks_in, nks_h = -(-DIR_IN // 16), DIR_HIDDEN // 16
+    assert S(1) - S(0) == nks_in and S(2) - S(1) == nks_h and S(6) - S(5) == nks_h
+    hid = _feat_table(lib.lnrf_host_hidden_feat, nks_in)
+    bit = np.array([[lib.lnrf_host_mask_bit(ks, j) for j in range(8)] for ks in range(nks_h)])
+    save = DumpLayout(lib, S(3), [TensorMap("xin", S(0), np.where(hid < DIR_IN, hid, -1), DIR_IN),
+                                  TensorMap("h9", S(1), hid[:nks_h], DIR_HIDDEN)],
+                      [MaskMap("mask9", S(2), hid[:nks_h], bit, DIR_HIDDEN)])
+    grad = DumpLayout(lib, S(6), [TensorMap("dy10", S(4), _dir_dy10_feat(lib, S(5) - S(4)), 3),
+                                  TensorMap("dy9", S(5), hid[:nks_h], DIR_HIDDEN)], [])
+    return save, grad
+
+
+def _decode(lay, buf_u8, m):
+    blocks, n_tiles = lay._blocks(buf_u8)
+    assert 0 < m <= n_tiles * lay.cols
+    out, pad, pad_slots = {}, {}, {}
+    for name in lay.tensors:
+        val, ps = lay.read(blocks, name)
+        out[name], pad[name] = _t(val[:m]), _t(val[m:])
+        if ps.shape[1]:
+            pad_slots[name] = _t(ps.astype(np.int32))
+    for name in lay.masks:
+        val = lay.read_mask(blocks, name)
+        out[name], pad[name] = _t(val[:m]), _t(val[m:])
+    out["pad"], out["pad_slots"] = pad, pad_slots
+    out["zero_slots"] = {s: _t(v) for s, v in _zero_slots(lay, blocks).items()}
+    return out, blocks, n_tiles
+
+
+def decode_dir_save(buf_u8, m):
+    """Directional save -> xin[m,273], h9[m,128] (float64), mask9[m,128] (bool); "pad": the same for the pad evaluations;
+    "pad_slots": raw uint16 of the k-slots 273..287 of xin (all rows); "mask9_high": the 8 bytes per lane of the mask slot that
+    carry no bit"""
+    lay, _ = dir_layouts()
+    out, blocks, n_tiles = _decode(lay, buf_u8, m)
+    k = lay.masks["mask9"]
+    lanes = blocks[:, k.slot * lay.frag_bytes:(k.slot + 1) * lay.frag_bytes].reshape(n_tiles, -1, 16)
+    out["mask9_high"] = _t(lanes[:, :, k.width // 16:].copy())
+    return out
+
+
+def decode_dir_grad(buf_u8, m):
+    """Directional gradient dump -> dy10[m,3], dy9[m,128]; "pad": the pad evaluations; "pad_slots": raw uint16 of the unused
+    k-slots of dy10, its whole second slot included (all rows).  Pass buf[:dir_grad_dump_bytes(m)]."""
+    return _decode(dir_layouts()[1], buf_u8, m)[0]
+
+
+def dir_grad_dump_bytes(m):
+    return padded_tiles(m) * dir_layouts()[1].tile_bytes()
+
+
+def _encode(lay, t, m):
+    n_tiles = padded_tiles(m)
+    blocks = np.zeros((n_tiles, lay.tile_bytes()), np.uint8)
+    for name in lay.tensors:
+        lay.write(blocks, name, _rows(t[name], n_tiles * lay.cols, lay.tensors[name].width))
+    for name in lay.masks:
+        lay.write_mask(blocks, name, _rows(t[name], n_tiles * lay.cols, lay.masks[name].width) != 0)
+    return blocks.reshape(-1)
+
+
+def encode_dir_save(t, m):
+    """inverse of decode_dir_save for xin, h9, mask9 of m rows (everything else stays zero)"""
+    return _encode(dir_layouts()[0], t, m)
+
+
+def encode_dir_grad(t, m):
+    return _encode(dir_layouts()[1], t, m)
 
 
 # ---- the two comparison rules -----------------------------------------------------------------------------------------

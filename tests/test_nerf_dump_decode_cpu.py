@@ -8,6 +8,8 @@ kernels, and the two comparison rules of test_gpu_nerf_stagewise.py.  No GPU inv
                       the way the kernel does (lane (c, hh) of slot F at dump_lane_off); the decoder must return the
                       emulator's activations in feature order, taken from the MFMA result map alone — a decoder that
                       permutes features consistently with its own encoder fails here
+  directional dumps   the same for the two dumps of the Ref-NeRF directional block (dir_layouts()): round trips, one owner per
+                      bit, the pad k-slots of xin and the empty second slot of dy10 identified, the kernel's fragment order
   the rules           accept the fp32-accumulated CPU result and reject each mutation a 3e-2 relative-L2 gate cannot see
 """
 import ctypes
@@ -194,6 +196,95 @@ def test_decode_is_vectorised(H):
     dt = time.perf_counter() - t0
     print(f"decode_save + decode_grad at m={m}: {dt:.3f} s")
     assert dt < 1.0
+
+
+# ---- Ref-NeRF directional block -------------------------------------------------------------------------------------------
+def random_dir(rng, m):
+    save = {"xin": rand_bf16(rng, m, D.DIR_IN), "h9": np.maximum(rand_bf16(rng, m, D.DIR_HIDDEN), 0),
+            "mask9": rng.random((m, D.DIR_HIDDEN)) < 0.5}
+    return save, {"dy10": rand_bf16(rng, m, 3), "dy9": rand_bf16(rng, m, D.DIR_HIDDEN)}
+
+
+@pytest.mark.parametrize("m", [1, 31, 32, 33, 70, 257])
+def test_dir_round_trip(H, m):
+    rng = np.random.default_rng(100 + m)
+    save, grad = random_dir(rng, m)
+    sl, gl = D.dir_layouts()
+    buf = D.encode_dir_save(save, m)
+    assert buf.size == D.padded_tiles(m) * sl.tile_bytes()
+    got = D.decode_dir_save(buf, m)
+    for name in save:
+        assert got[name].shape == save[name].shape and (got[name].numpy() == save[name]).all(), name
+    assert all(not v.numpy().any() for v in got["pad"].values()) and not got["mask9_high"].numpy().any()
+    assert set(got["pad_slots"]) == {"xin"} and not got["pad_slots"]["xin"].numpy().any() and not got["zero_slots"]
+    assert got["pad"]["xin"].shape == (32 * D.padded_tiles(m) - m, D.DIR_IN)
+    buf = D.encode_dir_grad(grad, m)
+    assert buf.size == D.dir_grad_dump_bytes(m)
+    got = D.decode_dir_grad(buf, m)
+    for name in grad:
+        assert got[name].shape == grad[name].shape and (got[name].numpy() == grad[name]).all(), name
+    assert all(not v.numpy().any() for v in got["pad"].values())
+    assert set(got["pad_slots"]) == {"dy10"} and not got["pad_slots"]["dy10"].numpy().any() and not got["zero_slots"]
+    # a single changed byte anywhere in a tensor's slots changes what is decoded
+    buf2 = buf.copy()
+    buf2[gl.pos["dy9"][m % 32 - 1, 127] * 2 + (m - 1) // 32 * gl.tile_bytes()] ^= 0x01
+    assert (D.decode_dir_grad(buf2, m)["dy9"].numpy() != grad["dy9"]).sum() == 1
+
+
+def test_dir_every_bit_has_one_owner_and_the_pads_are_identified(H):
+    """Per tile of the directional dumps every bit is one tensor element's or one mask bit's, except: the 15 k-slots of xin that
+    stand for inputs 273..287, the upper 8 bytes per lane of the mask slot (128 of its 256 bits per lane pair are used), and of
+    dy10 all but its 3 colour channels: 13 k-slots of its first slot and the whole second slot."""
+    save, grad = D.dir_layouts()
+    S = H.lnrf_host_dir_slot
+    assert save.n_slots == S(3) and grad.n_slots == S(6) and S(7) == -1
+    n_pad_in = 16 * save.tensors["xin"].nks - D.DIR_IN
+    for lay, free_bytes in ((save, 32 * 2 * n_pad_in + 64 * 8), (grad, 32 * 2 * 13 + save.frag_bytes)):
+        own = lay.bit_owners().reshape(-1, 8)
+        assert own.max() == 1, "two elements share a bit"
+        assert ((own.sum(1) == 8) | (own.sum(1) == 0)).all(), "a byte is partly owned"
+        assert int((own.sum(1) == 0).sum()) == free_bytes
+    # the pad k-slots of xin are those whose input feature does not exist, all in the last k-step
+    hid = np.array([[[H.lnrf_host_hidden_feat(ks, h, j) for j in range(8)] for h in range(2)] for ks in range(save.tensors["xin"].nks)])
+    feat = save.tensors["xin"].feat
+    assert ((feat == -1) == (hid >= D.DIR_IN)).all() and (feat == -1).sum() == n_pad_in == 15 and (feat[:-1] >= 0).all()
+    assert feat[-1, 0, 0] == D.DIR_IN - 1  # the scalar tail load: feature 272 alone in its k-step
+    # dy10: lane half 0 keeps channel j in element j (refnerf_dir_bwd_kernel), the second slot carries nothing
+    f10 = grad.tensors["dy10"].feat
+    assert f10.shape == (2, 2, 8) and (f10[1] == -1).all() and (f10[0, 1] == -1).all() and f10[0, 0].tolist() == [0, 1, 2] + [-1] * 5
+    # and the free regions are exactly what the decoders hand back
+    n = D.padded_tiles(1)
+    got = D.decode_dir_save(np.full(n * save.tile_bytes(), 0xFF, np.uint8), 1)
+    assert got["pad_slots"]["xin"].shape == (32 * n, n_pad_in) and (got["pad_slots"]["xin"].numpy() == 0xFFFF).all()
+    assert got["mask9_high"].numel() == n * 64 * 8 and got["mask9"].all()
+    got = D.decode_dir_grad(np.full(n * grad.tile_bytes(), 0xFF, np.uint8), 1)
+    assert got["pad_slots"]["dy10"].shape == (32 * n, 13 + 16) and (got["pad_slots"]["dy10"].numpy() == 0xFFFF).all()
+    second = grad.tensors["dy10"].slot0 + 1
+    assert second == S(4) + 1 == S(5) - 1
+    blocks = np.zeros((n, grad.tile_bytes()), np.uint8)
+    blocks[:, second * grad.frag_bytes:(second + 1) * grad.frag_bytes] = 0xFF
+    got = D.decode_dir_grad(blocks.reshape(-1), 1)
+    assert (got["pad_slots"]["dy10"].numpy() != 0).sum() == 32 * n * 16 and not got["dy10"].numpy().any() and not got["dy9"].numpy().any()
+
+
+def test_dir_decoder_against_the_fragment_order_of_the_kernel(H):
+    """refnerf_dir_fwd_kernel builds its input fragments from row[16 ks + 4 h + (0..3)] and row[16 ks + 8 + 4 h + (0..3)] and
+    stores fragment ks of lane (c, h) at dump_lane_off(slot, c, h); the decoder must hand the row back in feature order"""
+    save, _ = D.dir_layouts()
+    S = H.lnrf_host_dir_slot
+    rng = np.random.default_rng(9)
+    rows = rand_bf16(rng, 32, D.DIR_IN)
+    padded = np.zeros((32, 16 * save.tensors["xin"].nks))
+    padded[:, :D.DIR_IN] = rows
+    blocks = np.zeros((D.padded_tiles(32), save.tile_bytes()), np.uint8)
+    for ks in range(save.tensors["xin"].nks):
+        for c in range(32):
+            for h in range(2):
+                frag = np.concatenate([padded[c, 16 * ks + 4 * h:16 * ks + 4 * h + 4], padded[c, 16 * ks + 8 + 4 * h:16 * ks + 12 + 4 * h]])
+                off = (S(0) + ks) * save.frag_bytes + H.lnrf_host_dump_lane_off(S(0) + ks, c, h)
+                blocks[0, off:off + 16] = D.f64_to_bf16_bits(frag).view(np.uint8)
+    got = D.decode_dir_save(blocks.reshape(-1), 32)
+    assert (got["xin"].numpy() == rows).all() and not got["pad_slots"]["xin"].numpy().any()
 
 
 # ---- the rules ------------------------------------------------------------------------------------------------------------
