@@ -410,6 +410,7 @@ int lnrf_nerf_mlp_bwd_ls2(const lnrf_nerf_shape* shape, const void* packed_a, co
  *                               lnrf_nerf_shape) receives the bf16 activations and ReLU masks of the pass
  *   lnrf_refnerf_normal_pass    n_raw[m, 3] = -d spatial_out[:, 0] / dx (ref_nerf.py:38-43: the jax.grad inside
  *                               RefNERFBase.__call__); cdump (lnrf_nerf_bwd_scratch_bytes) keeps the chain states
+ *                               (zero for the pad evaluations m .. of the last tiles, like every gradient dump)
  *   lnrf_refnerf_trunk_bwd      grads += d L / d Dense_0..8 given g_spatial = d L / d spatial_out [m, ld]
  *                               (first-order path, on the layer-stationary pipeline of lnrf_nerf_mlp_bwd_ls;
  *                               scratch: lnrf_refnerf_trunk_bwd_scratch_bytes(m))

@@ -153,10 +153,11 @@ __global__ __launch_bounds__(kThreads) void refnerf_normal_kernel(
 
   DumpAddr gd{cdump, n_tiles, tile, c, h, kGradTileSlots};
   bf16x8 a0[16], a1[16];
-  // seed c_8 = -e_0: feature 0 is k slot (ks 0, h 0, j 0)
+  // seed c_8 = -e_0: feature 0 is k slot (ks 0, h 0, j 0).  Pad evaluations get no seed: their chain states are zero
+  // in the dump, as the gradients of pad evaluations are in every other dump
 #pragma unroll
   for (int i = 0; i < 16; ++i) a1[i] = zero_frag();
-  if (h == 0) a1[0][0] = (__bf16)(-1.0f);
+  if (h == 0 && valid) a1[0][0] = (__bf16)(-1.0f);
 #pragma unroll
   for (int i = 0; i < 16; ++i) stream_store(gd.at(grad_dy_slot(8) + i), frag_to_bits(a1[i]));
 
