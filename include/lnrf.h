@@ -631,6 +631,40 @@ int lnrf_rt_closest(const lnrf_rt_bvh* bvh, const float* sorted_tris, const int3
 int lnrf_rt_occluded(const lnrf_rt_bvh* bvh, const float* sorted_tris, const float* nodes, const float* rays,
                      const float* window, int64_t m, uint8_t* out, lnrf_stream_t stream);
 
+/* ------------------------------------------------------ dataset diagnostics ---- */
+
+/* Whole-view reductions behind scripts/cv_nerf.py and scripts/check_bbox.py (csrc/view_stats.hip), with a FIXED order
+ * of combination: workgroups of 256 whose count min(ceil(n / 256), 1024) depends on the problem size only leave one
+ * partial each in `scratch` (8-byte aligned; every partial that is read is written first), and a second launch of one
+ * workgroup folds the partials into the caller's accumulator — bit-reproducible on any device.  No entry point
+ * allocates, copies, synchronises or uses atomics. */
+
+/* *acc += S, S = sum_n sum_c (double(outputs[n, c]) - double(targets[n * target_stride + c]))^2 with every operation in
+ * fp64: the numerator of the mean squared error of TrainLoop.losses (train.py:141-142), the deterministic counterpart
+ * of the sq_err atomic of lnrf_composite_fwd.  outputs [n, 3] fp32; targets: rows of target_stride >= 3 floats (9 for
+ * the colour column of an [n, 3, 3] batch); ray_err (nullable) [n] fp32 receives float(sum_c ...) per ray; acc: one
+ * device double, which successive calls on one stream may share.  NaN / Inf propagate.  n == 0 returns LNRF_OK and
+ * touches nothing.  scratch: lnrf_sq_err_scratch_bytes(n) bytes (-1 for n < 0). */
+int64_t lnrf_sq_err_scratch_bytes(int64_t n);
+int lnrf_sq_err_f64(const float* outputs, const float* targets, int64_t target_stride, int64_t n, float* ray_err,
+                    double* acc, void* scratch, int64_t scratch_bytes, lnrf_stream_t stream);
+
+/* The pixels of a view whose ray misses the scene box (scripts/check_bbox.py:31-46): for every pixel in raster order
+ * the ray of CameraView.bare_rays (dataset.py:52-78, the arithmetic of lnrf_camera_rays) is tested with ray_t_range
+ * (render.py:346-389, the arithmetic of lnrf_ray_aabb_stratified), and the pixels whose mask is false are combined
+ * into stats (device int64 [10]): [0] += count, [1..3] += sums of the uint8 channel values, [4..6] = min(., channel
+ * minima), [7..9] = max(., channel maxima) — the caller initialises [4..6] to 255 and [7..9] to 0, and may run several
+ * views into one stats.  Integer arithmetic: exact.  image: uint8 [height, width, 3]; miss (nullable): uint8
+ * [height * width], 1 for a ray that misses, 0 for one that hits.  origin / axes / bbox_min / bbox_max: (host) 3 floats
+ * each; fields of view in radians.  width, height >= 1 and width * height <= INT32_MAX, else LNRF_ERR_SHAPE (scratch
+ * bytes: -1); a width or height of 1 uses the -1 end of the linspace, like lnrf_camera_rays.
+ * scratch: lnrf_view_miss_scratch_bytes(width, height) bytes. */
+int64_t lnrf_view_miss_scratch_bytes(int32_t width, int32_t height);
+int lnrf_view_miss_stats(const float* origin, const float* x_axis, const float* y_axis, const float* z_axis,
+                         float x_fov, float y_fov, int32_t width, int32_t height, const uint8_t* image,
+                         const float* bbox_min, const float* bbox_max, float min_t_range, float epsilon, uint8_t* miss,
+                         int64_t* stats, void* scratch, int64_t scratch_bytes, lnrf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

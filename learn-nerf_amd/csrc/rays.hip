@@ -2,41 +2,9 @@
 // needed).  Reference: learn_nerf/render.py (file:line cited per kernel).
 #include "common.h"
 #include "philox.h"
+#include "ray_geom.h"  // TRange / ray_t_range, BBox, Camera / camera_pixel_ray
 
 namespace lnrf {
-
-// ---------------------------------------------------------------------------------------
-// ray_t_range (render.py:346-389), computed per ray.
-struct TRange {
-  float t_min, t_max;
-  bool mask;
-};
-
-__device__ __forceinline__ TRange ray_t_range(const float* __restrict__ ray, const float bmin[3],
-                                              const float bmax[3], float min_t_range, float eps) {
-  float lo = -INFINITY, hi = INFINITY;
-#pragma unroll
-  for (int a = 0; a < 3; ++a) {
-    const float o = ray[a], d = ray[3 + a];
-    const float den = d + eps;                 // render.py:371 (epsilon added, not sign-matched)
-    const float t0 = (bmin[a] - o) / den;      // render.py:370-371
-    const float t1 = (bmax[a] - o) / den;
-    lo = fmaxf(lo, fminf(t0, t1));             // render.py:374-383
-    hi = fminf(hi, fmaxf(t0, t1));             // render.py:384
-  }
-  const float min_t = fmaxf(0.0f, lo);         // render.py:383
-  const float max_t = hi;
-  const float max_c = fmaxf(max_t, min_t + min_t_range);  // render.py:385
-  TRange r;
-  r.mask = min_t < max_t;                      // render.py:388
-  r.t_min = r.mask ? min_t : 0.0f;             // render.py:389 null_range
-  r.t_max = r.mask ? max_c : min_t_range;
-  return r;
-}
-
-struct BBox {
-  float mn[3], mx[3];
-};
 
 __global__ void ray_aabb_stratified_kernel(const float* __restrict__ rays, int64_t ray_stride,
                                            int64_t n_rays, BBox bb, float min_t_range, float eps,
@@ -497,33 +465,16 @@ __global__ void bin_edges_kernel(const float* __restrict__ ts, const float* __re
   }
 }
 
-// CameraView.bare_rays (dataset.py:52-78): pixel (px, py) in raster order ->
-// direction = normalize(z + tan(x_fov/2) * lx[px] * x_axis + tan(y_fov/2) * ly[py] * y_axis),
-// lx = linspace(-1, 1, W), ly = linspace(-1, 1, H) (end points inclusive); origin = camera origin.
-struct Camera {
-  float origin[3], x_axis[3], y_axis[3], z_axis[3];
-  float tan_x, tan_y;
-};
+// CameraView.bare_rays (dataset.py:52-78): every pixel's ray (camera_pixel_ray, ray_geom.h) in raster order
 __global__ void camera_rays_kernel(Camera cam, int width, int height, float* __restrict__ rays) {
   const int64_t total = (int64_t)width * height;
   for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total;
        e += (int64_t)gridDim.x * blockDim.x) {
     const int py = (int)(e / width), px = (int)(e - (int64_t)py * width);
-    const float lx = width > 1 ? -1.0f + 2.0f * (float)px / (float)(width - 1) : -1.0f;
-    const float ly = height > 1 ? -1.0f + 2.0f * (float)py / (float)(height - 1) : -1.0f;
-    float d[3];
-    float nrm = 0.0f;
+    float ray[6];
+    camera_pixel_ray(cam, width, height, px, py, ray);
 #pragma unroll
-    for (int a = 0; a < 3; ++a) {
-      d[a] = (cam.tan_x * lx) * cam.x_axis[a] + (cam.tan_y * ly) * cam.y_axis[a] + cam.z_axis[a];
-      nrm += d[a] * d[a];
-    }
-    nrm = sqrtf(nrm);
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-      rays[e * 6 + a] = cam.origin[a];
-      rays[e * 6 + 3 + a] = d[a] / nrm;
-    }
+    for (int a = 0; a < 6; ++a) rays[e * 6 + a] = ray[a];
   }
 }
 
@@ -729,15 +680,7 @@ extern "C" int lnrf_camera_rays(const float* origin, const float* x_axis, const 
                                 lnrf_stream_t stream) {
   LNRF_CHECK_ARG(origin && x_axis && y_axis && z_axis && rays, "null pointer");
   LNRF_CHECK_ARG(width >= 1 && height >= 1, "bad image size");
-  Camera cam;
-  for (int a = 0; a < 3; ++a) {
-    cam.origin[a] = origin[a];
-    cam.x_axis[a] = x_axis[a];
-    cam.y_axis[a] = y_axis[a];
-    cam.z_axis[a] = z_axis[a];
-  }
-  cam.tan_x = tanf(x_fov * 0.5f);
-  cam.tan_y = tanf(y_fov * 0.5f);
+  const Camera cam = make_camera(origin, x_axis, y_axis, z_axis, x_fov, y_fov);
   hipLaunchKernelGGL(camera_rays_kernel, dim3(grid_for((int64_t)width * height, 256)), dim3(256), 0,
                      as_stream(stream), cam, (int)width, (int)height, rays);
   LNRF_LAUNCH_CHECK();

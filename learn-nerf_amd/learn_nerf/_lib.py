@@ -162,6 +162,11 @@ PROTOTYPES = {
     "lnrf_rt_fit": (c_int32, [POINTER(RtBvh), _P, _P, _P]),
     "lnrf_rt_closest": (c_int32, [POINTER(RtBvh), _P, _P, _P, _P, _P, c_int64, _P, _P, _P]),
     "lnrf_rt_occluded": (c_int32, [POINTER(RtBvh), _P, _P, _P, _P, c_int64, _P, _P]),
+    "lnrf_sq_err_scratch_bytes": (c_int64, [c_int64]),
+    "lnrf_sq_err_f64": (c_int32, [_P, _P, c_int64, c_int64, _P, _P, _P, c_int64, _P]),
+    "lnrf_view_miss_scratch_bytes": (c_int64, [c_int32, c_int32]),
+    "lnrf_view_miss_stats": (c_int32, [_F3, _F3, _F3, _F3, c_float, c_float, c_int32, c_int32, _P, _F3, _F3, c_float,
+                                       c_float, _P, _P, _P, c_int64, _P]),
 }
 
 _lib = None

@@ -444,3 +444,55 @@ def sq_norm_into(x: torch.Tensor, out: torch.Tensor):
     """out (1-element fp32, pre-zeroed by the caller) += sum(x^2)"""
     L.check(L.lib().lnrf_sq_norm(L.ptr(x), x.numel(), L.ptr(out), L.stream()), "sq_norm")
     return out
+
+
+# ---------------------------------------------------------------- dataset diagnostics
+
+def _scratch(nbytes: int, device) -> torch.Tensor:
+    # written by the first launch before the second reads it: plain uninitialised memory
+    return torch.empty(max(int(nbytes), 8), dtype=torch.uint8, device=device)
+
+
+def sq_err_f64_(outputs: torch.Tensor, targets: torch.Tensor, acc: torch.Tensor,
+                ray_err: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """acc (one float64 element, e.g. a slot acc_all[v:v + 1]) += sum((outputs - targets)^2) in fp64 and in a fixed
+    order (lnrf_sq_err_f64).  targets [n, 3] may be the strided colour column batch[:, 2] of an [n, 3, 3] batch;
+    ray_err [n] fp32 (optional) receives the per-ray sums."""
+    n = outputs.shape[0]
+    if outputs.shape != (n, 3) or targets.shape != (n, 3) or (n and targets.stride(1) != 1):
+        raise ValueError("sq_err_f64_: outputs and targets must be [n, 3] with unit channel stride")
+    if acc.numel() != 1 or acc.dtype != torch.float64:
+        raise ValueError("sq_err_f64_: acc must be one float64 element")
+    if ray_err is not None and ray_err.numel() != n:
+        raise ValueError("sq_err_f64_: ray_err must hold n floats")
+    if n == 0:
+        return acc
+    if not targets.is_cuda or targets.dtype != F32:
+        raise RuntimeError("lnrf kernels need fp32 tensors on a ROCm GPU device (no CPU fallback)")
+    nbytes = L.lib().lnrf_sq_err_scratch_bytes(n)
+    scratch = _scratch(nbytes, _dev(outputs))
+    L.check(L.lib().lnrf_sq_err_f64(L.ptr(outputs), L.c_void_p(targets.data_ptr()), targets.stride(0), n,
+                                    L.ptr(ray_err), L.ptr(acc, torch.float64), L.ptr(scratch, torch.uint8), nbytes,
+                                    L.stream()), "sq_err_f64")
+    return acc
+
+
+def view_miss_stats_(view, image_u8: torch.Tensor, bbox_min: Sequence[float], bbox_max: Sequence[float],
+                     stats: torch.Tensor, miss: Optional[torch.Tensor] = None, min_t_range: float = 1e-3,
+                     epsilon: float = 1e-8) -> torch.Tensor:
+    """Combine the pixels of image_u8 (device uint8 [H, W, 3]) whose ray from the CameraView `view` misses the box into
+    stats (device int64 [10]: count, channel sums, minima, maxima; the caller starts the minima at 255 and the maxima at
+    0) — lnrf_view_miss_stats.  miss (optional, device uint8 [H * W]) receives 1 per missing ray."""
+    if image_u8.dim() != 3 or image_u8.shape[2] != 3:
+        raise ValueError("view_miss_stats_: image must be [H, W, 3]")
+    height, width = int(image_u8.shape[0]), int(image_u8.shape[1])
+    if stats.numel() != 10 or (miss is not None and miss.numel() != height * width):
+        raise ValueError("view_miss_stats_: stats holds 10 int64 words, miss one byte per pixel")
+    nbytes = L.lib().lnrf_view_miss_scratch_bytes(width, height)  # -1 for a shape the call below rejects
+    scratch = _scratch(nbytes, _dev(stats))
+    L.check(L.lib().lnrf_view_miss_stats(
+        L.f3(view.camera_origin), L.f3(view.x_axis), L.f3(view.y_axis), L.f3(view.camera_direction), float(view.x_fov),
+        float(view.y_fov), width, height, L.ptr(image_u8, torch.uint8), L.f3(bbox_min), L.f3(bbox_max),
+        float(min_t_range), float(epsilon), L.ptr(miss, torch.uint8), L.ptr(stats, torch.int64),
+        L.ptr(scratch, torch.uint8), nbytes, L.stream()), "view_miss_stats")
+    return stats
