@@ -665,6 +665,38 @@ int lnrf_view_miss_stats(const float* origin, const float* x_axis, const float* 
                          const float* bbox_min, const float* bbox_max, float min_t_range, float epsilon, uint8_t* miss,
                          int64_t* stats, void* scratch, int64_t scratch_bytes, lnrf_stream_t stream);
 
+/* ------------------------------------------------------------- occupancy ---- */
+
+/* Occupancy grid for the inference renderer (additive: the reference samples every ray over its whole box range).
+ * Conventions, passes and the walk's pad: the header comments of csrc/occupancy.hip and csrc/occ_geom.h.
+ * lnrf_occ_build: sigma fp32 [(R+1)^3], densities at the cell-corner lattice in C order, R = resolution in [1, 512]
+ * (else LNRF_ERR_SHAPE; scratch bytes -1).  Cell (i, j, k) is raw-occupied iff some corner has NOT (sigma < sigma_thr)
+ * (NaN and +inf occupy), occupied iff a raw-occupied cell lies within Chebyshev distance dilate >= 0.  bits: uint32
+ * [ceil(R^3 / 32)], cell (i*R + j)*R + k = bit idx & 31 of word idx >> 5, unused bits of the last word zero; count: one
+ * device int64, the occupied cells (integer sums in a fixed order, no atomics).
+ * scratch: lnrf_occ_scratch_bytes(R) bytes, 16-byte aligned. */
+int64_t lnrf_occ_scratch_bytes(int32_t resolution);
+int lnrf_occ_build(const float* sigma, int32_t resolution, float sigma_thr, int32_t dilate, uint32_t* bits,
+                   int64_t* count, void* scratch, int64_t scratch_bytes, lnrf_stream_t stream);
+
+/* Clips the (t_min, t_max, mask) of lnrf_ray_aabb_stratified (same rays, ray_stride, box, min_t_range and epsilon) to
+ * the occupied cells each ray crosses, one ray per lane: t_min' = max(t_min, t_first - pad), t_max' = min(t_max,
+ * max(t_last + pad, t_min' + min_t_range)), mask' = mask & (an occupied cell was crossed), the null range
+ * (0, min_t_range) where mask' is 0.  A full grid returns its inputs bit for bit.  The outputs may be the inputs. */
+int lnrf_occ_clip_rays(const float* rays, int64_t ray_stride, int64_t n_rays, const float* bbox_min,
+                       const float* bbox_max, const uint32_t* bits, int32_t resolution, float min_t_range,
+                       float epsilon, const float* t_min, const float* t_max, const uint8_t* mask, float* t_min_out,
+                       float* t_max_out, uint8_t* mask_out, lnrf_stream_t stream);
+
+/* idx[0..count) = the indices of the non-zero bytes of mask [n] in ascending order (idx holds n int32), count: one
+ * device int64 that the host reads back.  Deterministic: a scan, no atomics.  n <= INT32_MAX, else LNRF_ERR_SHAPE. */
+int lnrf_compact_mask(const uint8_t* mask, int64_t n, int32_t* idx, int64_t* count, lnrf_stream_t stream);
+
+/* The inverse of lnrf_gather_rows: out[idx[i], :] = src[i, :] for i < n, rows of row_floats fp32, out of n_out rows.
+ * Rows that idx does not name are left as they are; an index outside [0, n_out) is skipped; idx must not repeat. */
+int lnrf_scatter_rows(const float* src, int32_t row_floats, const int32_t* idx, int64_t n, float* out, int64_t n_out,
+                      lnrf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -355,6 +355,8 @@ class InstantNGPRefNERFModel(ModelBase):
     lnrf_hashgrid_jvp / lnrf_hashgrid_bwd_dir.
     """
 
+    AUX_NAMES = ("normal_mse", "neg_normal")
+
     sh_degree: int = 4
     table_sizes: Sequence[int] = None
     grid_sizes: Sequence[int] = None

@@ -38,6 +38,8 @@ class ModelBase:
     Subclasses provide param_spec(), _forward(flat, x, d, rays, ts, save) and _backward(...).
     """
 
+    AUX_NAMES = ()  # the keys of the aux dict that forward_points / forward_rays return
+
     def param_spec(self) -> List[Tuple[str, str, Tuple[int, ...]]]:
         raise NotImplementedError
 

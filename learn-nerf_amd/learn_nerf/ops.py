@@ -65,6 +65,62 @@ def gather_rows_into(src: torch.Tensor, idx: torch.Tensor, out: torch.Tensor) ->
     return out
 
 
+def scatter_rows_into(src: torch.Tensor, idx: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
+    """out[idx[i], :] = src[i, :] for fp32 row matrices on the GPU; the other rows of `out` keep their values."""
+    if src.dim() != 2 or out.dim() != 2 or src.shape[1] != out.shape[1] or idx.shape[0] != src.shape[0]:
+        raise ValueError("scatter_rows_into: shape mismatch")
+    L.check(L.lib().lnrf_scatter_rows(L.ptr(src), src.shape[1], L.ptr(idx, torch.int32), idx.shape[0], L.ptr(out),
+                                      out.shape[0], L.stream()), "scatter_rows")
+    return out
+
+
+def compact_mask(mask: torch.Tensor) -> torch.Tensor:
+    """Indices (int32, ascending) of the non-zero entries of a uint8 mask [N]; reads the count back once."""
+    n = mask.shape[0]
+    idx = torch.empty(n, dtype=torch.int32, device=_dev(mask))
+    count = torch.empty(1, dtype=torch.int64, device=_dev(mask))
+    L.check(L.lib().lnrf_compact_mask(L.ptr(mask, torch.uint8), n, L.ptr(idx, torch.int32),
+                                      L.ptr(count, torch.int64), L.stream()), "compact_mask")
+    return idx[:int(count.item())]
+
+
+def occ_build(sigma: torch.Tensor, resolution: int, sigma_thr: float, dilate: int) -> Tuple[torch.Tensor, int]:
+    """Occupancy bitfield (int32 words holding the uint32 bit patterns) of corner densities sigma [(R+1)^3], and the
+    number of occupied cells."""
+    r = int(resolution)
+    if sigma.numel() != (r + 1) ** 3:
+        raise ValueError(f"occ_build: {sigma.numel()} corner densities for resolution {r}, expected {(r + 1) ** 3}")
+    lib = L.lib()
+    nbytes = lib.lnrf_occ_scratch_bytes(r)
+    if nbytes < 0:
+        raise ValueError(f"occ_build: resolution {r} is not supported")
+    dev = _dev(sigma)
+    scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    bits = torch.empty((r ** 3 + 31) // 32, dtype=torch.int32, device=dev)
+    count = torch.empty(1, dtype=torch.int64, device=dev)
+    L.check(lib.lnrf_occ_build(L.ptr(sigma), r, float(sigma_thr), int(dilate), L.ptr(bits, torch.int32),
+                               L.ptr(count, torch.int64), L.ptr(scratch, torch.uint8), nbytes, L.stream()),
+            "occ_build")
+    return bits, int(count.item())
+
+
+def occ_clip_rays(rays, bbox_min: Sequence[float], bbox_max: Sequence[float], bits: torch.Tensor, resolution: int,
+                  t_min, t_max, mask, min_t_range: float = 1e-3, epsilon: float = 1e-8):
+    """(t_min, t_max, mask) of ray_aabb_stratified clipped to the occupied cells of `bits` -> new tensors."""
+    n = rays.shape[0]
+    dev = _dev(rays)
+    if bits.numel() != (int(resolution) ** 3 + 31) // 32:
+        raise ValueError("occ_clip_rays: bitfield size does not match the resolution")
+    lo = torch.empty(n, dtype=F32, device=dev)
+    hi = torch.empty(n, dtype=F32, device=dev)
+    out_mask = torch.empty(n, dtype=torch.uint8, device=dev)
+    L.check(L.lib().lnrf_occ_clip_rays(
+        L.ptr(rays), _ray_stride(rays), n, L.f3(bbox_min), L.f3(bbox_max), L.ptr(bits, torch.int32), int(resolution),
+        min_t_range, epsilon, L.ptr(t_min), L.ptr(t_max), L.ptr(mask, torch.uint8), L.ptr(lo), L.ptr(hi),
+        L.ptr(out_mask, torch.uint8), L.stream()), "occ_clip_rays")
+    return lo, hi, out_mask
+
+
 def stratified(t_min, t_max, count: int, u=None, seed: int = 0, stream_id: int = 0, ray_offset: int = 0):
     n = t_min.shape[0]
     ts = torch.empty((n, count), dtype=F32, device=_dev(t_min))

@@ -52,6 +52,8 @@ def spherical_harmonic(sh_degree: int, coords: torch.Tensor) -> torch.Tensor:
 class RefNERFBase(ModelBase):
     """A base class for Ref-NeRF models (ref_nerf.py:19-77)."""
 
+    AUX_NAMES = ("normal_mse", "neg_normal")
+
     sh_degree: int = 4
 
 

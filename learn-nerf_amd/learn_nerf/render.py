@@ -4,12 +4,13 @@ learn_nerf.render — NeRFRenderer, RaySamples, render_rays, ray_t_range
 torch tensors on the GPU and every arithmetic step is a HIP kernel behind include/lnrf.h.
 """
 from dataclasses import dataclass
-from typing import Any, Dict, Sequence, Tuple
+from typing import Any, Dict, Optional, Sequence, Tuple
 
 import torch
 
 from . import ops
 from .model import ModelBase
+from .occupancy import OccupancyGrid
 from .rng import KeyLike, sampler_args, split
 
 STREAM_COARSE = 0  # Philox stream ids (oracle/philox.py)
@@ -34,6 +35,8 @@ class NeRFRenderer:
     :param coarse / fine: the models.  :param coarse_params / fine_params: their parameter trees.
     :param background: the [3] RGB background tensor.  :param bbox_min / bbox_max: scene bounds.
     :param coarse_ts: samples per ray for the coarse model.  :param fine_ts: additional fine samples.
+    :param occupancy: optional OccupancyGrid (additive, inference only): ray ranges are clipped to its occupied cells
+                      and the models run on the rays that cross one; None renders exactly as the reference does.
     """
 
     coarse: ModelBase
@@ -47,6 +50,7 @@ class NeRFRenderer:
     fine_ts: int
 
     min_t_range: float = 1e-3
+    occupancy: Optional[OccupancyGrid] = None
 
     def render_rays(self, key: KeyLike, batch: torch.Tensor) -> Dict[str, Dict[str, torch.Tensor]]:
         """
@@ -54,6 +58,8 @@ class NeRFRenderer:
         :param batch: an [N x 2 x 3] (or [N x 3 x 3]) batch of (origin, direction[, colour]) rays.
         :return: dict with keys "fine", "coarse", "fine_aux", "coarse_aux" (render.py:86-91).
         """
+        if self.occupancy is not None:
+            return self._render_rays_clipped(key, batch)
         coarse_key, fine_key = split(key, 2)  # render.py:55
         ca = sampler_args(coarse_key, STREAM_COARSE)
         t_min, t_max, mask, ts = ops.ray_aabb_stratified(  # render.py:53, 57-63
@@ -63,6 +69,26 @@ class NeRFRenderer:
         fine_ts = coarse_ts.fine_sampling(count=self.fine_ts, key=fine_key,
                                           densities=coarse_out["densities"])  # render.py:73-77
         fine_out, fine_aux = render_rays(self.fine, self.fine_params, self.background, batch, fine_ts)
+        return dict(coarse=coarse_out, fine=fine_out, coarse_aux=coarse_aux, fine_aux=fine_aux)
+
+    def _render_rays_clipped(self, key: KeyLike, batch: torch.Tensor) -> Dict[str, Dict[str, torch.Tensor]]:
+        """
+        render_rays with the occupancy grid.  Sampling and compositing run on the whole batch, so every Philox element
+        index is the ray's index in the batch, and outputs, alphas, coords and the aux means are those of render_rays
+        run with the clipped (t_min, t_max, mask); only the models run on the compacted live rays (mask' != 0).  The
+        per-sample densities, rgbs (and aux losses) of the other rays are zero: nothing evaluates them.
+        """
+        coarse_key, fine_key = split(key, 2)
+        batch = batch.contiguous()
+        t_min, t_max, mask, _ = ops.ray_aabb_stratified(batch, _vec3(self.bbox_min), _vec3(self.bbox_max), 0,
+                                                        min_t_range=self.min_t_range)
+        t_min, t_max, mask = self.occupancy.clip(batch, t_min, t_max, mask, min_t_range=self.min_t_range)
+        coarse_ts = RaySamples.stratified_sampling(t_min, t_max, mask, self.coarse_ts, coarse_key)
+        live = ops.compact_mask(mask)  # the one read-back per batch: the number of live rays
+        coarse_out, coarse_aux = render_rays(self.coarse, self.coarse_params, self.background, batch, coarse_ts,
+                                             live=live)
+        fine_ts = coarse_ts.fine_sampling(count=self.fine_ts, key=fine_key, densities=coarse_out["densities"])
+        fine_out, fine_aux = render_rays(self.fine, self.fine_params, self.background, batch, fine_ts, live=live)
         return dict(coarse=coarse_out, fine=fine_out, coarse_aux=coarse_aux, fine_aux=fine_aux)
 
     def t_range(self, batch: torch.Tensor, epsilon: float = 1e-8):
@@ -143,16 +169,46 @@ class RaySamples:
         return ops.termination_probs(self.ts, self.t_min, self.t_max, densities.contiguous())
 
 
+def _forward_live(model: ModelBase, flat: torch.Tensor, batch: torch.Tensor, ts: torch.Tensor, live: torch.Tensor):
+    """model.forward_rays on the rows `live` (int32, ascending) of the batch, scattered back into zero-filled
+    [N, T], [N, T, 3] and aux [N, T] arrays.  No model kernel runs when `live` is empty."""
+    n, t = ts.shape
+    dev = ts.device
+    densities = torch.zeros((n, t), dtype=torch.float32, device=dev)
+    rgbs = torch.zeros((n, t, 3), dtype=torch.float32, device=dev)
+    aux = {name: torch.zeros((n, t), dtype=torch.float32, device=dev) for name in model.AUX_NAMES}
+    m = live.shape[0]
+    if m == 0:
+        return densities, rgbs, aux
+    rows = batch.view(n, -1)
+    live_rays = ops.gather_rows_into(rows, live, torch.empty((m, rows.shape[1]), dtype=torch.float32, device=dev))
+    live_ts = ops.gather_rows_into(ts, live, torch.empty((m, t), dtype=torch.float32, device=dev))
+    d_live, c_live, aux_live, _ = model.forward_rays(flat, live_rays.view(m, *batch.shape[1:]), live_ts, save=False)
+    ops.scatter_rows_into(d_live.reshape(m, t).contiguous(), live, densities)
+    ops.scatter_rows_into(c_live.reshape(m, t * 3).contiguous(), live, rgbs.view(n, t * 3))
+    if set(aux_live) != set(aux):
+        raise RuntimeError(f"{type(model).__name__}.AUX_NAMES {sorted(aux)} != forward_rays aux {sorted(aux_live)}")
+    for name, values in aux_live.items():
+        ops.scatter_rows_into(values.reshape(m, t).contiguous(), live, aux[name])
+    return densities, rgbs, aux
+
+
 def render_rays(model: ModelBase, params: Any, background: torch.Tensor, batch: torch.Tensor,
-                ts: RaySamples) -> Tuple[Dict[str, torch.Tensor], Dict[str, torch.Tensor]]:
+                ts: RaySamples, live: Optional[torch.Tensor] = None
+                ) -> Tuple[Dict[str, torch.Tensor], Dict[str, torch.Tensor]]:
     """
     Render a batch of rays using a model (render.py:293-343).
 
+    :param live: optional int32 row numbers (ascending, as ops.compact_mask gives them) of the rays to evaluate the
+                 model on; the samples of every other ray get density 0 and rgb 0 (additive, for the occupancy grid).
     :return: (out, aux): out has outputs[N,3], rgbs[N,T,3], densities[N,T], alphas[N,1], coords[N,3];
              aux maps loss names to scalar means over rays.
     """
     flat = model.flat(params)
-    densities, rgbs, aux, _ = model.forward_rays(flat, batch, ts.ts, save=False)  # render.py:318-327
+    if live is None:
+        densities, rgbs, aux, _ = model.forward_rays(flat, batch, ts.ts, save=False)  # render.py:318-327
+    else:
+        densities, rgbs, aux = _forward_live(model, flat, batch, ts.ts, live)
     names = list(aux.keys())
     stacked = torch.stack([aux[k] for k in names], dim=-1).contiguous() if names else None
     outputs, alphas, coords, aux_sum = ops.composite_fwd(batch, ts.ts, ts.t_min, ts.t_max, _mask_u8(ts.mask),

@@ -11,6 +11,7 @@ import numpy as np
 import torch
 
 from learn_nerf.dataset import CameraView, ModelMetadata
+from learn_nerf.occupancy import OccupancyGrid
 from learn_nerf.render import NeRFRenderer
 from learn_nerf.rng import Key
 from learn_nerf.scripts.train_nerf import add_model_args, create_model
@@ -24,6 +25,10 @@ RENDER_FLAGS = (
     ("--width", int, 512, None),
     ("--height", int, 512, None),
     ("--model_path", str, "nerf.pkl", None),
+    # additive (no counterpart in the reference): skip empty space with an occupancy grid of the fine model
+    ("--occupancy_grid", int, 0, "cells per axis of the occupancy grid; 0 = off (render every sample)"),
+    ("--occupancy_threshold", float, 0.01, "opacity of one cell diagonal below which a cell counts as empty"),
+    ("--occupancy_dilate", int, 1, "cells by which the occupied set is grown"),
 )
 
 
@@ -55,6 +60,13 @@ class RenderSession:
                                      fine_params=params["fine"], background=params["background"],
                                      bbox_min=self.metadata.bbox_min, bbox_max=self.metadata.bbox_max,
                                      coarse_ts=args.coarse_samples, fine_ts=args.fine_samples)
+        resolution = getattr(args, "occupancy_grid", 0)
+        if resolution > 0:
+            grid = OccupancyGrid.from_renderer(self.renderer, resolution, threshold=args.occupancy_threshold,
+                                               dilate=args.occupancy_dilate)
+            print(f"occupancy grid {resolution}^3: {grid.occupied} of {resolution ** 3} cells occupied "
+                  f"({100.0 * grid.occupied_fraction:.2f}%)")
+            self.renderer.occupancy = grid
         self.key = Key(args.seed if args.seed is not None else random.randint(0, 2 ** 32 - 1))
         self.args = args
         self.images = []
