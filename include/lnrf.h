@@ -665,6 +665,25 @@ int lnrf_view_miss_stats(const float* origin, const float* x_axis, const float* 
                          const float* bbox_min, const float* bbox_max, float min_t_range, float epsilon, uint8_t* miss,
                          int64_t* stats, void* scratch, int64_t scratch_bytes, lnrf_stream_t stream);
 
+/* --------------------------------------------------------- image metrics ---- */
+
+/* SSIM of two images (csrc/image_metrics.hip; learn_nerf/metrics.py, scripts/eval_nerf.py), Wang et al. 2004 as
+ * skimage.metrics.structural_similarity(gaussian_weights=True, sigma=1.5, use_sample_covariance=False, data_range=1,
+ * channel_axis=-1) computes it: a, b fp32 [height, width, 3] in [0, 1], each channel on its own; 11 x 11 Gaussian
+ * window g[i] = exp(-(i - 5)^2 / (2 * 1.5^2)) normalised to sum 1 and applied separably; VALID region only, no padding;
+ * population moments s_xx = filt(x x) - mu_x^2 (likewise s_yy, s_xy), not clamped; C1 = 0.01^2, C2 = 0.03^2;
+ * ssim = (2 mu_x mu_y + C1)(2 s_xy + C2) / ((mu_x^2 + mu_y^2 + C1)(s_xx + s_yy + C2)).  Taps, moments, ratio and sum
+ * are fp64.  ssim_map (nullable): double [height - 10, width - 10, 3]; *acc (one device double, which successive calls
+ * on one stream may share) += the sum of the map's entries — the view's SSIM is that sum / (3 (height - 10)(width - 10)).
+ * The order of summation is fixed, by the scheme of the dataset diagnostics above: min(tiles, 1024) workgroups of 256,
+ * tiles = 3 * ceil((height - 10) / 16) * ceil((width - 10) / 32), leave one partial each in `scratch` (8-byte aligned;
+ * every partial that is read is written first) and a second launch of one workgroup folds them into *acc.  No atomics,
+ * allocation, copy or synchronisation.  NaN / Inf propagate.  width, height >= 11 and width * height <= INT32_MAX, else
+ * LNRF_ERR_SHAPE (scratch bytes: -1).  scratch: lnrf_ssim_scratch_bytes(width, height) bytes. */
+int64_t lnrf_ssim_scratch_bytes(int32_t width, int32_t height);
+int lnrf_ssim_f64(const float* a, const float* b, int32_t width, int32_t height, double* ssim_map, double* acc,
+                  void* scratch, int64_t scratch_bytes, lnrf_stream_t stream);
+
 /* ------------------------------------------------------------- occupancy ---- */
 
 /* Occupancy grid for the inference renderer (additive: the reference samples every ray over its whole box range).

@@ -8,31 +8,15 @@
 // Launch 2: one workgroup of 256; thread t combines the partials 4t, 4t+1, 4t+2, 4t+3 (< grid) in that order, then the
 // same butterfly and the same four-wave fold, and thread 0 combines the result into the caller's accumulator.
 // No atomics, no allocation, no synchronisation with the host; launch 1 writes every partial that launch 2 reads.
+// The constants, the butterfly and the fp64 fold are in stat_reduce.h, which csrc/image_metrics.hip shares.
 #include "ray_geom.h"
+#include "stat_reduce.h"
 
 namespace lnrf {
-
-constexpr int kStatBlock = 256;
-constexpr int kStatMaxGrid = 1024;
-constexpr int kStatPerFoldThread = kStatMaxGrid / kStatBlock;  // partials per thread of the fold launch
 
 static inline int stat_grid(int64_t n) {
   const int64_t g = (n + kStatBlock - 1) / kStatBlock;
   return (int)(g < kStatMaxGrid ? g : kStatMaxGrid);
-}
-
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-
-// sum over the workgroup, valid in thread 0: butterfly per wave, then the four waves in order
-__device__ __forceinline__ double block_sum_f64(double v, double* s_part) {
-  v = wave_sum_f64(v);
-  if ((threadIdx.x & 63) == 0) s_part[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return ((s_part[0] + s_part[1]) + s_part[2]) + s_part[3];
 }
 
 // ---------------------------------------------------------------------------------------
@@ -61,14 +45,7 @@ __global__ __launch_bounds__(kStatBlock) void sq_err_partial_kernel(const float*
 __global__ __launch_bounds__(kStatBlock) void sq_err_fold_kernel(const double* __restrict__ parts, int n_parts,
                                                                  double* __restrict__ acc) {
   __shared__ double s_part[kStatBlock / 64];
-  double s = 0.0;
-#pragma unroll
-  for (int k = 0; k < kStatPerFoldThread; ++k) {
-    const int b = (int)threadIdx.x * kStatPerFoldThread + k;
-    if (b < n_parts) s += parts[b];
-  }
-  const double total = block_sum_f64(s, s_part);
-  if (threadIdx.x == 0) acc[0] += total;
+  fold_partials_f64(parts, n_parts, acc, s_part);
 }
 
 // ---------------------------------------------------------------------------------------

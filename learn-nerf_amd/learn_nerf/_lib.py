@@ -167,6 +167,8 @@ PROTOTYPES = {
     "lnrf_view_miss_scratch_bytes": (c_int64, [c_int32, c_int32]),
     "lnrf_view_miss_stats": (c_int32, [_F3, _F3, _F3, _F3, c_float, c_float, c_int32, c_int32, _P, _F3, _F3, c_float,
                                        c_float, _P, _P, _P, c_int64, _P]),
+    "lnrf_ssim_scratch_bytes": (c_int64, [c_int32, c_int32]),
+    "lnrf_ssim_f64": (c_int32, [_P, _P, c_int32, c_int32, _P, _P, _P, c_int64, _P]),
     "lnrf_occ_scratch_bytes": (c_int64, [c_int32]),
     "lnrf_occ_build": (c_int32, [_P, c_int32, c_float, c_int32, _P, _P, _P, c_int64, _P]),
     "lnrf_occ_clip_rays": (c_int32, [_P, c_int64, c_int64, _F3, _F3, _P, c_int32, c_float, c_float, _P, _P, _P, _P,

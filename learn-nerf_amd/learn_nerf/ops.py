@@ -533,6 +533,35 @@ def sq_err_f64_(outputs: torch.Tensor, targets: torch.Tensor, acc: torch.Tensor,
     return acc
 
 
+SSIM_WINDOW = 11  # taps of the Gaussian window of lnrf_ssim_f64: the smallest image side
+
+
+def ssim_f64_(a: torch.Tensor, b: torch.Tensor, acc: torch.Tensor,
+              ssim_map: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """acc (one float64 element) += the sum of the SSIM map of the unit images a, b (fp32 [H, W, 3] in [0, 1],
+    contiguous): 11 x 11 Gaussian window, sigma 1.5, valid region, fp64, fixed order (lnrf_ssim_f64).  ssim_map
+    (optional, float64 [H - 10, W - 10, 3]) receives the map."""
+    if a.dim() != 3 or a.shape[2] != 3 or a.shape != b.shape:
+        raise ValueError("ssim_f64_: a and b must be [H, W, 3] images of one shape")
+    height, width = int(a.shape[0]), int(a.shape[1])
+    if height < SSIM_WINDOW or width < SSIM_WINDOW:
+        raise ValueError(f"ssim_f64_: images of {width} x {height} pixels are smaller than the "
+                         f"{SSIM_WINDOW} x {SSIM_WINDOW} window")
+    if acc.numel() != 1 or acc.dtype != torch.float64:
+        raise ValueError("ssim_f64_: acc must be one float64 element")
+    if ssim_map is not None and (ssim_map.shape != (height - SSIM_WINDOW + 1, width - SSIM_WINDOW + 1, 3)
+                                 or ssim_map.dtype != torch.float64):
+        raise ValueError("ssim_f64_: ssim_map must be float64 [H - 10, W - 10, 3]")
+    if not (a.is_cuda and b.is_cuda) or a.dtype != F32 or b.dtype != F32:
+        raise RuntimeError("lnrf kernels need fp32 tensors on a ROCm GPU device (no CPU fallback)")
+    nbytes = L.lib().lnrf_ssim_scratch_bytes(width, height)  # -1 for a shape the call below rejects
+    scratch = _scratch(nbytes, _dev(a))
+    L.check(L.lib().lnrf_ssim_f64(L.ptr(a), L.ptr(b), width, height, L.ptr(ssim_map, torch.float64),
+                                  L.ptr(acc, torch.float64), L.ptr(scratch, torch.uint8), nbytes, L.stream()),
+            "ssim_f64")
+    return acc
+
+
 def view_miss_stats_(view, image_u8: torch.Tensor, bbox_min: Sequence[float], bbox_max: Sequence[float],
                      stats: torch.Tensor, miss: Optional[torch.Tensor] = None, min_t_range: float = 1e-3,
                      epsilon: float = 1e-8) -> torch.Tensor:
