@@ -28,6 +28,10 @@ class NerfShape(ctypes.Structure):
                 ("input_layers", "mid_layers", "hidden_dim", "color_layer_dim", "x_freqs", "d_freqs")]
 
 
+# the shape the fused NeRF kernels cover; the fused Ref-NeRF trunk's buffers have the same layout (read-only)
+FUSED_NERF_SHAPE = NerfShape(5, 4, 256, 128, 10, 4)
+
+
 class NgpMlpDesc(ctypes.Structure):
     _fields_ = [("enc_dim", c_int32), ("hidden_dim", c_int32), ("density_dim", c_int32),
                 ("density_layers", c_int32), ("color_layers", c_int32), ("d_freqs", c_int32),

@@ -7,11 +7,9 @@ sweep so one level's table stays L2-resident); the tiny MLP is the fused bf16 MF
 csrc/ngp_mlp.hip (precision="bf16", default) or the exact-fp32 strided GEMM (precision="fp32").
 Parameter tree names follow Flax: MultiresHashTableEncoding_0/HashTableEncoding_{l}/table, Dense_0..4.
 """
-from dataclasses import dataclass, field
-from typing import Any, Dict, List, Sequence, Tuple
-
 import ctypes
-from collections import OrderedDict
+from dataclasses import dataclass
+from typing import List, Sequence, Tuple
 
 import torch
 
@@ -19,8 +17,9 @@ from . import _lib as L
 from . import _prof
 from . import _ws
 from . import ops
-from .model import ModelBase
-from .params import lecun_normal_
+from .model import ModelBase, pack_buffer
+from .params import dense_spec, dense_views, init_dense_
+from .ref_nerf import aux_dict, aux_grads
 
 F32 = torch.float32
 POISON_SCRATCH = False  # tests set this: scratch buffers are filled with 0xFF bytes (NaN) before the kernels run
@@ -116,13 +115,6 @@ class InstantNGPModel(ModelBase):
     render_precision: str = "bf16x3"
     tag: str = "ngp"
 
-    _pack_cache: Any = field(default=None, repr=False, compare=False)
-    _pack_generation: int = field(default=0, repr=False, compare=False)
-
-    def invalidate_packed(self) -> None:
-        """Call after the parameters were modified outside torch (e.g. by lnrf_adam_step)."""
-        self._pack_generation += 1
-
     def encoding(self) -> MultiresHashTableEncoding:
         return MultiresHashTableEncoding(self.table_sizes, self.grid_sizes, self.bbox_min, self.bbox_max,
                                          self.table_feature_dim, self.table_smooth)
@@ -144,31 +136,11 @@ class InstantNGPModel(ModelBase):
 
     def packed_weights(self, flat: torch.Tensor, kind: str = "bf16") -> torch.Tensor:
         """bf16 MFMA-fragment copy of the Dense parameters ("bf16": forward + transposed streams; "split": hi/lo pairs
-        of the forward stream for the render kernel); rebuilt when the flat buffer changes.  As in
-        NeRFModel.packed_weights: a miss packs into a fresh buffer (a saved backward context may hold the old
-        one) and cache entries keep their source tensor alive so that a recycled address cannot hit."""
-        if self._pack_cache is None:
-            self._pack_cache = OrderedDict()
-        key = (kind, flat.data_ptr(), flat.numel(), flat._version, str(flat.device), self._pack_generation)
-        hit = self._pack_cache.get(key)
-        if hit is not None:
-            self._pack_cache.move_to_end(key)
-            return hit[1]
-        desc = self._mlp_desc()
-        if kind == "split":
-            nbytes = L.lib().lnrf_ngp_mlp_packed_split_bytes(ctypes.byref(desc))
-            packed = torch.empty(nbytes, dtype=torch.uint8, device=flat.device)
-            L.check(L.lib().lnrf_ngp_mlp_pack_split(ctypes.byref(desc), L.ptr(flat), L.ptr(packed, torch.uint8),
-                                                    L.stream()), "ngp_mlp_pack_split")
-        else:
-            nbytes = L.lib().lnrf_ngp_mlp_packed_bytes(ctypes.byref(desc))
-            packed = torch.empty(nbytes, dtype=torch.uint8, device=flat.device)
-            L.check(L.lib().lnrf_ngp_mlp_pack(ctypes.byref(desc), L.ptr(flat), L.ptr(packed, torch.uint8), L.stream()),
-                    "ngp_mlp_pack")
-        self._pack_cache[key] = (flat, packed)
-        while len(self._pack_cache) > 6:
-            self._pack_cache.popitem(last=False)
-        return packed
+        of the forward stream for the render kernel), cached by ModelBase._packed."""
+        lib = L.lib()
+        calls = ((lib.lnrf_ngp_mlp_packed_split_bytes, lib.lnrf_ngp_mlp_pack_split, "ngp_mlp_pack_split")
+                 if kind == "split" else (lib.lnrf_ngp_mlp_packed_bytes, lib.lnrf_ngp_mlp_pack, "ngp_mlp_pack"))
+        return self._packed(kind, flat, 6, lambda: pack_buffer(flat, *calls, ctypes.byref(self._mlp_desc())))
 
     def _fused_forward_points(self, flat, x, d, save: bool):
         enc = self.encoding()
@@ -233,33 +205,18 @@ class InstantNGPModel(ModelBase):
         return dims
 
     def param_spec(self):
-        spec = []
-        for l, r in enumerate(self.encoding().rows()):
-            spec.append((f"MultiresHashTableEncoding_0/HashTableEncoding_{l}", "table", (r, self.table_feature_dim)))
-        for i, (fi, fo) in enumerate(self.dense_dims()):
-            spec.append((f"Dense_{i}", "kernel", (fi, fo)))
-            spec.append((f"Dense_{i}", "bias", (fo,)))
-        return spec
+        return [(f"MultiresHashTableEncoding_0/HashTableEncoding_{l}", "table", (r, self.table_feature_dim))
+                for l, r in enumerate(self.encoding().rows())] + dense_spec(self.dense_dims())
 
     def init_flat_(self, flat, gen):
         nt = self.encoding().num_table_floats()
         u = torch.rand(nt, generator=gen, dtype=torch.float32)
         flat[:nt] = 1e-4 * (u * 2 - 1)  # instant_ngp.py:181-185
-        off = nt
-        for fi, fo in self.dense_dims():
-            lecun_normal_(flat[off:off + fi * fo].view(fi, fo), fi, gen)
-            off += fi * fo + fo
+        init_dense_(flat, self.dense_dims(), gen, nt)
 
     def _dense_views(self, flat):
         nt = self.encoding().num_table_floats()
-        out, off = [], nt
-        for fi, fo in self.dense_dims():
-            k = flat[off:off + fi * fo].view(fi, fo)
-            off += fi * fo
-            b = flat[off:off + fo]
-            off += fo
-            out.append((k, b))
-        return flat[:nt], out
+        return flat[:nt], dense_views(flat, self.dense_dims(), nt)
 
     @ops.uses_model_precision
     def forward_points(self, flat, x, d, save: bool):
@@ -423,7 +380,7 @@ class InstantNGPRefNERFModel(ModelBase):
             li += 1
         dir_out = ops.dense_fwd(c, W[li][0], W[li][1], L.ACT_NONE)
         rgb = ops.refnerf_color_fwd(dir_out, spectral, diffuse)
-        aux = dict(normal_mse=aux2[:, 0], neg_normal=aux2[:, 1])
+        aux = aux_dict(aux2)
         ctx = None
         if save:
             ctx = dict(flat=flat, x=x, d=d, enc_t=enc_t, h0=h0, dir_in=dir_in, c0=c0, c1=c1, g_enc_t=g_enc_t,
@@ -439,10 +396,7 @@ class InstantNGPRefNERFModel(ModelBase):
         x, d, h0, dir_in, cacts = ctx["x"], ctx["d"], ctx["h0"], ctx["dir_in"], ctx["cacts"]
         m, dev, hd, dd = x.shape[0], grad_flat.device, self.hidden_dim, self.density_dim
         lf = len(self.grid_sizes) * self.table_feature_dim
-        if g_aux is None:
-            g_aux2 = torch.zeros((m, 2), dtype=F32, device=dev)
-        else:
-            g_aux2 = torch.stack([g_aux["normal_mse"].reshape(-1), g_aux["neg_normal"].reshape(-1)], 1).contiguous()
+        g_aux2 = aux_grads(g_aux, m, dev)
         g_do, g_sp, g_df = ops.refnerf_color_bwd(ctx["dir_out"], ctx["spectral"], ctx["diffuse"],
                                                  g_rgb.reshape(-1, 3).contiguous())
         li = len(W) - 1

@@ -17,7 +17,7 @@ import os
 import warnings
 from collections import OrderedDict
 from dataclasses import dataclass, field
-from typing import ClassVar, Any, Dict, List, Optional, Tuple
+from typing import Callable, ClassVar, Dict, List, Tuple
 
 import torch
 
@@ -25,7 +25,8 @@ from . import _lib as L
 from . import _prof
 from . import _ws
 from . import ops
-from .params import ParamTree, as_generator, build_tree, default_device, flat_of, lecun_normal_, spec_size
+from .params import (ParamTree, as_generator, build_tree, default_device, dense_spec, dense_views, flat_of, init_dense_,
+                     spec_size)
 
 F32 = torch.float32
 
@@ -39,6 +40,33 @@ class ModelBase:
     """
 
     AUX_NAMES = ()  # the keys of the aux dict that forward_points / forward_rays return
+    _pack_cache = None  # OrderedDict of _packed(), or None = empty (tests reset it that way)
+    _pack_generation = 0
+
+    def invalidate_packed(self) -> None:
+        """Call after the parameters were modified outside torch (e.g. by lnrf_adam_step)."""
+        self._pack_generation += 1
+
+    def _packed(self, kind: str, flat: torch.Tensor, capacity: int, pack: Callable[[], torch.Tensor]) -> torch.Tensor:
+        """
+        The packed copy `kind` of the parameters `flat`, from a small LRU cache that maps (kind, storage address, size,
+        version, device, generation) to the buffer pack() returned.  Every miss packs into a FRESH buffer — a saved
+        backward context may still hold the previous one (e.g. one model instance serving as coarse and fine) — and
+        every entry keeps a reference to its source tensor, so a freed temporary's address cannot come back as a
+        stale hit.
+        """
+        if self._pack_cache is None:
+            self._pack_cache = OrderedDict()
+        key = (kind, flat.data_ptr(), flat.numel(), flat._version, str(flat.device), self._pack_generation)
+        hit = self._pack_cache.get(key)
+        if hit is not None:
+            self._pack_cache.move_to_end(key)
+            return hit[1]
+        packed = pack()
+        self._pack_cache[key] = (flat, packed)
+        while len(self._pack_cache) > capacity:
+            self._pack_cache.popitem(last=False)
+        return packed
 
     def param_spec(self) -> List[Tuple[str, str, Tuple[int, ...]]]:
         raise NotImplementedError
@@ -96,8 +124,7 @@ def ls_status(ctx) -> int:
     buf = ctx.get("ls_scratch")
     if buf is None:
         return 0
-    shape = L.NerfShape(5, 4, 256, 128, 10, 4)
-    off = L.lib().lnrf_nerf_bwd_ls_status_offset(ctypes.byref(shape), ctx["m"])
+    off = L.lib().lnrf_nerf_bwd_ls_status_offset(ctypes.byref(L.FUSED_NERF_SHAPE), ctx["m"])
     return int(buf[off:off + 4].view(torch.int32).item())
 
 
@@ -105,7 +132,7 @@ def backward_ls_pair(ctx_a, g_density_a, g_rgb_a, grad_a, ctx_b, g_density_b, g_
     """The layer-stationary backward of TWO fused NeRFModel contexts (train.py:141-142: coarse and fine) in one persistent
     launch (lnrf_nerf_mlp_bwd_ls2): the pipelines of the chip are shared in proportion to the evaluations, so the coarse
     pass does not pay a pipeline fill and drain of its own.  grad_a / grad_b += d L / d params."""
-    shape = L.NerfShape(5, 4, 256, 128, 10, 4)
+    shape = L.FUSED_NERF_SHAPE
     lib = L.lib()
     dev = grad_a.device
     la = _ws.lease("nerf_bwd_ls", lib.lnrf_nerf_bwd_ls_scratch_bytes(ctypes.byref(shape), ctx_a["m"]), dev)
@@ -144,6 +171,48 @@ def sinusoidal_emb(coords: torch.Tensor, freqs: int) -> torch.Tensor:
     return out.reshape(shape[:-1] + (shape[-1] * 2 * freqs,))
 
 
+def pack_buffer(flat: torch.Tensor, nbytes, fill, what: str, *desc) -> torch.Tensor:
+    """A fresh uint8 buffer of nbytes(*desc) bytes, filled by the pack entry fill(*desc, flat, buffer, stream)."""
+    packed = torch.empty(nbytes(*desc), dtype=torch.uint8, device=flat.device)
+    L.check(fill(*desc, L.ptr(flat), L.ptr(packed, torch.uint8), L.stream()), what)
+    return packed
+
+
+# ---- the NeRF trunk (model.py:50-56), shared by NeRFModel and RefNERFModel: input_layers Dense + ReLU on the
+# embedding, the skip concat [z, x_emb], mid_layers Dense with a ReLU between them (the last one is linear)
+def nerf_trunk_dims(x_emb_width: int, input_layers: int, mid_layers: int, hidden_dim: int) -> List[Tuple[int, int]]:
+    return ([(hidden_dim if i else x_emb_width, hidden_dim) for i in range(input_layers)]
+            + [(hidden_dim if i else hidden_dim + x_emb_width, hidden_dim) for i in range(mid_layers)])
+
+
+def nerf_trunk_fwd(W, x, x_freqs: int, input_layers: int, mid_layers: int, dst):
+    """The trunk on the dense GEMM path; W = [(kernel, bias)] views.  The last mid layer writes into dst, the [M, hidden]
+    head of the next block's concat buffer.  -> cat_x = [z, x_emb] and the outputs of all the trunk's layers
+    (acts[input_layers - 1] aliases cat_x[:, :hidden], acts[-1] is dst)."""
+    m, hd = x.shape[0], W[0][0].shape[1]
+    cat_x = torch.empty((m, hd + 6 * x_freqs), dtype=F32, device=W[0][0].device)  # [z, x_emb] (model.py:52)
+    ops.sinusoidal_emb_into(x, x_freqs, cat_x, hd)
+    acts, z, ns = [], cat_x[:, hd:], input_layers + mid_layers
+    for l in range(ns):
+        if l == input_layers:
+            z = cat_x
+        out = cat_x[:, :hd] if l == input_layers - 1 else (dst if l == ns - 1 else None)
+        z = ops.dense_fwd(z, W[l][0], W[l][1], L.ACT_NONE if l == ns - 1 else L.ACT_RELU, out=out)
+        acts.append(z)
+    return cat_x, acts
+
+
+def nerf_trunk_bwd(W, G, cat_x, acts, input_layers: int, mid_layers: int, gy) -> None:
+    """First-order backward of nerf_trunk_fwd: G[l] += d L / d Dense_l given gy = d L / d (the last mid layer's linear
+    output); acts[l] = the output of Dense_l, read for l < input_layers + mid_layers - 1."""
+    hd = gy.shape[1]
+    for l in reversed(range(input_layers + mid_layers)):
+        inp = cat_x if l == input_layers else (cat_x[:, hd:] if l == 0 else acts[l - 1])
+        ops.dense_bwd_weight(inp, gy, G[l][0], G[l][1])
+        if l > 0:  # input gradient + ReLU backward of the layer below
+            gy = ops.dense_bwd_input(gy, W[l][0][:hd], gate=acts[l - 1])
+
+
 @dataclass
 class NeRFModel(ModelBase):
     """
@@ -169,8 +238,6 @@ class NeRFModel(ModelBase):
     # so that the kernel timers of bench.py stay meaningful; LNRF_OVERLAP_BACKWARD=1 turns it on.
     overlap_backward_hint: ClassVar[bool] = False
 
-    _pack_cache: Any = field(default=None, repr=False, compare=False)
-    _pack_generation: int = field(default=0, repr=False, compare=False)
     _warned_dense: bool = field(default=False, repr=False, compare=False)
 
     def __post_init__(self):
@@ -181,38 +248,17 @@ class NeRFModel(ModelBase):
         if min(self.hidden_dim, self.color_layer_dim, self.x_freqs, self.d_freqs) < 1:
             raise ValueError("NeRFModel widths and frequency counts must be positive")
 
-    def invalidate_packed(self) -> None:
-        """Call after the parameters were modified outside torch (e.g. by lnrf_adam_step)."""
-        self._pack_generation += 1
-
     # ---- structure ---------------------------------------------------------------------------
     def layer_dims(self) -> List[Tuple[int, int]]:
-        xe, de = 6 * self.x_freqs, 6 * self.d_freqs
-        dims, fan = [], xe
-        for _ in range(self.input_layers):
-            dims.append((fan, self.hidden_dim))
-            fan = self.hidden_dim
-        fan = self.hidden_dim + xe
-        for _ in range(self.mid_layers):
-            dims.append((fan, self.hidden_dim))
-            fan = self.hidden_dim
-        dims.append((self.hidden_dim, 1))
-        dims.append((self.hidden_dim + de, self.color_layer_dim))
-        dims.append((self.color_layer_dim, 3))
-        return dims
+        hd = self.hidden_dim
+        return nerf_trunk_dims(6 * self.x_freqs, self.input_layers, self.mid_layers, hd) + [
+            (hd, 1), (hd + 6 * self.d_freqs, self.color_layer_dim), (self.color_layer_dim, 3)]
 
     def param_spec(self):
-        spec = []
-        for i, (fi, fo) in enumerate(self.layer_dims()):
-            spec.append((f"Dense_{i}", "kernel", (fi, fo)))
-            spec.append((f"Dense_{i}", "bias", (fo,)))
-        return spec
+        return dense_spec(self.layer_dims())
 
     def init_flat_(self, flat, gen):
-        off = 0
-        for fi, fo in self.layer_dims():
-            lecun_normal_(flat[off:off + fi * fo].view(fi, fo), fi, gen)
-            off += fi * fo + fo  # bias stays zero (Flax default)
+        init_dense_(flat, self.layer_dims(), gen)
 
     def _shape_struct(self) -> L.NerfShape:
         return L.NerfShape(self.input_layers, self.mid_layers, self.hidden_dim, self.color_layer_dim,
@@ -238,34 +284,12 @@ class NeRFModel(ModelBase):
     def packed_weights(self, flat: torch.Tensor, kind: str = "bf16") -> torch.Tensor:
         """
         MFMA-fragment copy of the parameters: kind "bf16" (forward + transposed streams, training) or
-        "split" (bf16 hi/lo pairs, rendering).  A small cache maps (storage address, size, version, generation)
-        to the packed buffer.  Every miss packs into a FRESH buffer — a saved backward context may still hold
-        the previous one (e.g. one model instance serving as coarse and fine) — and every entry keeps a
-        reference to its source tensor, so a freed temporary's address cannot come back as a stale hit.
+        "split" (bf16 hi/lo pairs, rendering), cached by ModelBase._packed.
         """
-        if self._pack_cache is None:
-            self._pack_cache = OrderedDict()
-        key = (kind, flat.data_ptr(), flat.numel(), flat._version, str(flat.device), self._pack_generation)
-        hit = self._pack_cache.get(key)
-        if hit is not None:
-            self._pack_cache.move_to_end(key)
-            return hit[1]
-        shape = self._shape_struct()
         lib = L.lib()
-        if kind == "split":
-            nbytes = lib.lnrf_nerf_packed_split_bytes(ctypes.byref(shape))
-            packed = torch.empty(nbytes, dtype=torch.uint8, device=flat.device)
-            L.check(lib.lnrf_nerf_pack_weights_split(ctypes.byref(shape), L.ptr(flat), L.ptr(packed, torch.uint8),
-                                                     L.stream()), "nerf_pack_weights_split")
-        else:
-            nbytes = lib.lnrf_nerf_packed_bytes(ctypes.byref(shape))
-            packed = torch.empty(nbytes, dtype=torch.uint8, device=flat.device)
-            L.check(lib.lnrf_nerf_pack_weights(ctypes.byref(shape), L.ptr(flat), L.ptr(packed, torch.uint8),
-                                               L.stream()), "nerf_pack_weights")
-        self._pack_cache[key] = (flat, packed)
-        while len(self._pack_cache) > 4:
-            self._pack_cache.popitem(last=False)
-        return packed
+        calls = ((lib.lnrf_nerf_packed_split_bytes, lib.lnrf_nerf_pack_weights_split, "nerf_pack_weights_split")
+                 if kind == "split" else (lib.lnrf_nerf_packed_bytes, lib.lnrf_nerf_pack_weights, "nerf_pack_weights"))
+        return self._packed(kind, flat, 4, lambda: pack_buffer(flat, *calls, ctypes.byref(self._shape_struct())))
 
     def _fused_fwd(self, flat, m, save, x=None, d=None, rays=None, ts=None):
         shape = self._shape_struct()
@@ -355,30 +379,12 @@ class NeRFModel(ModelBase):
     # ---- exact fp32 dense path (any shape) ------------------------------------------------------
     @ops.uses_model_precision
     def _dense_fwd(self, flat, x, d, save: bool):
-        tree = self.tree(flat)
-        W = [(tree[f"Dense_{i}"]["kernel"], tree[f"Dense_{i}"]["bias"]) for i in range(len(self.layer_dims()))]
-        m, dev, hd = x.shape[0], flat.device, self.hidden_dim
-        xe_w, de_w = 6 * self.x_freqs, 6 * self.d_freqs
-        cat_x = torch.empty((m, hd + xe_w), dtype=F32, device=dev)  # [z, x_emb] (model.py:52)
-        ops.sinusoidal_emb_into(x, self.x_freqs, cat_x, hd)
-        x_emb = cat_x[:, hd:]
-        acts = []
-        z = x_emb
-        li = 0
-        for i in range(self.input_layers):  # model.py:50-51
-            out = cat_x[:, :hd] if i == self.input_layers - 1 else None
-            z = ops.dense_fwd(z, W[li][0], W[li][1], L.ACT_RELU, out=out)
-            acts.append(z)
-            li += 1
-        cat_d = torch.empty((m, hd + de_w), dtype=F32, device=dev)  # [z, d_emb] (model.py:58)
+        W = dense_views(flat, self.layer_dims())
+        m, hd = x.shape[0], self.hidden_dim
+        cat_d = torch.empty((m, hd + 6 * self.d_freqs), dtype=F32, device=flat.device)  # [z, d_emb] (model.py:58)
         ops.sinusoidal_emb_into(d, self.d_freqs, cat_d, hd)
-        z = cat_x
-        for i in range(self.mid_layers):  # model.py:53-56: relu precedes Dense for i > 0
-            last = i == self.mid_layers - 1
-            z = ops.dense_fwd(z, W[li][0], W[li][1], L.ACT_NONE if last else L.ACT_RELU,
-                              out=cat_d[:, :hd] if last else None)
-            acts.append(z)
-            li += 1
+        cat_x, acts = nerf_trunk_fwd(W, x, self.x_freqs, self.input_layers, self.mid_layers, cat_d[:, :hd])
+        li = self.input_layers + self.mid_layers
         density = ops.dense_fwd(cat_d[:, :hd], W[li][0], W[li][1], L.ACT_SOFTPLUS)  # model.py:57
         li += 1
         h_col = ops.dense_fwd(cat_d, W[li][0], W[li][1], L.ACT_RELU)  # model.py:59
@@ -392,33 +398,19 @@ class NeRFModel(ModelBase):
 
     @ops.uses_model_precision
     def _dense_bwd(self, ctx, g_density, g_rgb, grad_flat):
-        tree, gtree = self.tree(ctx["flat"]), self.tree(grad_flat)
-        nl = len(self.layer_dims())
-        W = [tree[f"Dense_{i}"]["kernel"] for i in range(nl)]
-        G = [(gtree[f"Dense_{i}"]["kernel"], gtree[f"Dense_{i}"]["bias"]) for i in range(nl)]
-        hd = self.hidden_dim
-        cat_x, cat_d, acts, h_col = ctx["cat_x"], ctx["cat_d"], ctx["acts"], ctx["h_col"]
+        dims = self.layer_dims()
+        W = dense_views(ctx["flat"], dims)
+        G = dense_views(grad_flat, dims)
+        hd, nl = self.hidden_dim, len(dims)
+        cat_d, h_col = ctx["cat_d"], ctx["h_col"]
         i_rgb, i_col, i_den = nl - 1, nl - 2, nl - 3
         gy = ops.act_bwd_(g_rgb.reshape(-1, 3).clone(), ctx["rgb"], L.ACT_TANH)
         ops.dense_bwd_weight(h_col, gy, *G[i_rgb])
-        gy = ops.dense_bwd_input(gy, W[i_rgb], gate=h_col)  # ReLU backward of Dense_10 fused in
+        gy = ops.dense_bwd_input(gy, W[i_rgb][0], gate=h_col)  # ReLU backward of Dense_10 fused in
         ops.dense_bwd_weight(cat_d, gy, *G[i_col])
-        gz = ops.dense_bwd_input(gy, W[i_col][:hd])
+        gz = ops.dense_bwd_input(gy, W[i_col][0][:hd])
         gd = ops.act_bwd_(g_density.reshape(-1, 1).clone(), ctx["density"], L.ACT_SOFTPLUS)
         z_view = cat_d[:, :hd]
         ops.dense_bwd_weight(z_view, gd, *G[i_den])
-        ops.dense_bwd_input(gd, W[i_den], out=gz, accumulate=True)
-        gy = gz  # Dense_{last mid} output is linear
-        li = i_den - 1
-        for i in reversed(range(self.mid_layers)):
-            inp = cat_x if i == 0 else acts[self.input_layers + i - 1]
-            ops.dense_bwd_weight(inp, gy, *G[li])
-            prev = cat_x[:, :hd] if i == 0 else acts[self.input_layers + i - 1]
-            gy = ops.dense_bwd_input(gy, W[li][:hd], gate=prev)  # input gradient + ReLU backward of the layer below
-            li -= 1
-        for i in reversed(range(self.input_layers)):
-            inp = cat_x[:, hd:] if i == 0 else acts[i - 1]
-            ops.dense_bwd_weight(inp, gy, *G[li])
-            if i > 0:
-                gy = ops.dense_bwd_input(gy, W[li], gate=acts[i - 1])
-            li -= 1
+        ops.dense_bwd_input(gd, W[i_den][0], out=gz, accumulate=True)
+        nerf_trunk_bwd(W, G, ctx["cat_x"], ctx["acts"], self.input_layers, self.mid_layers, gz)

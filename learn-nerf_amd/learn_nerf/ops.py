@@ -4,6 +4,7 @@ with torch (device memory plumbing only) and enqueues one HIP kernel family on t
 stream.  No arithmetic happens in Python.
 """
 import contextlib
+import ctypes
 import functools
 from typing import Optional, Sequence, Tuple
 
@@ -356,8 +357,6 @@ def gemm(a: torch.Tensor, sa_i: int, sa_r: int, b: torch.Tensor, sb_r: int, sb_j
 
 
 def hashgrid_fwd(desc, tables: torch.Tensor, x: torch.Tensor) -> torch.Tensor:
-    import ctypes
-
     m = x.shape[0]
     enc_t = torch.empty((desc.n_levels * desc.feature_dim, m), dtype=F32, device=_dev(x))
     L.check(L.lib().lnrf_hashgrid_fwd(ctypes.byref(desc), L.ptr(tables), L.ptr(x), m, L.ptr(enc_t), L.stream()),
@@ -367,8 +366,6 @@ def hashgrid_fwd(desc, tables: torch.Tensor, x: torch.Tensor) -> torch.Tensor:
 
 def hashgrid_jvp(desc, tables: torch.Tensor, x: torch.Tensor, u: torch.Tensor) -> torch.Tensor:
     """(d enc / d x) u in the feature-major layout [L*F, M]"""
-    import ctypes
-
     m = x.shape[0]
     out = torch.empty((desc.n_levels * desc.feature_dim, m), dtype=F32, device=_dev(x))
     L.check(L.lib().lnrf_hashgrid_jvp(ctypes.byref(desc), L.ptr(tables), L.ptr(x), L.ptr(u), m, L.ptr(out),
@@ -378,8 +375,6 @@ def hashgrid_jvp(desc, tables: torch.Tensor, x: torch.Tensor, u: torch.Tensor) -
 
 def hashgrid_input_grad(desc, tables: torch.Tensor, x: torch.Tensor, g_enc_t: torch.Tensor) -> torch.Tensor:
     """(d enc / d x)^T g_enc -> [M, 3]"""
-    import ctypes
-
     m = x.shape[0]
     g_x = torch.empty((m, 3), dtype=F32, device=_dev(x))
     L.check(L.lib().lnrf_hashgrid_input_grad(ctypes.byref(desc), L.ptr(tables), L.ptr(x), m, L.ptr(g_enc_t),
@@ -394,8 +389,6 @@ def hashgrid_bwd_dir(desc, x: torch.Tensor, u: torch.Tensor, g_enc_t: torch.Tens
 def hashgrid_bwd(desc, x: torch.Tensor, g_enc_t: torch.Tensor, g_tables: torch.Tensor, u=None, level_absmax=None):
     """g_tables += scatter(g_enc_t); hashed levels go through the bucketed (atomic-free) path.  level_absmax
     (u is None only): per-level upper bound of |g_enc_t| from the kernel that wrote it (lnrf_ngp_mlp_bwd)."""
-    import ctypes
-
     m = x.shape[0]
     nbytes = L.lib().lnrf_hashgrid_bwd_scratch_bytes(ctypes.byref(desc), m)
     lease = _ws.lease("hashgrid_bwd", max(int(nbytes), 16), _dev(x))

@@ -64,6 +64,27 @@ def lecun_normal_(w: torch.Tensor, fan_in: int, generator: torch.Generator) -> N
     w.copy_(tmp * (math.sqrt(1.0 / fan_in) / 0.87962566103423978))
 
 
+def dense_spec(dims: Sequence[Tuple[int, int]]) -> List[Tuple[str, str, Tuple[int, ...]]]:
+    """spec rows of a stack of Dense layers, dims = [(fan_in, fan_out)]: Dense_{i} kernel [in,out], bias [out]."""
+    return [row for i, (fi, fo) in enumerate(dims)
+            for row in ((f"Dense_{i}", "kernel", (fi, fo)), (f"Dense_{i}", "bias", (fo,)))]
+
+
+def dense_views(flat: torch.Tensor, dims: Sequence[Tuple[int, int]], off: int = 0):
+    """[(kernel, bias)] views of the Dense stack that starts at float `off` of a flat buffer."""
+    out = []
+    for fi, fo in dims:
+        out.append((flat[off:off + fi * fo].view(fi, fo), flat[off + fi * fo:off + fi * fo + fo]))
+        off += fi * fo + fo
+    return out
+
+
+def init_dense_(flat: torch.Tensor, dims: Sequence[Tuple[int, int]], generator: torch.Generator, off: int = 0) -> None:
+    """Flax nn.Dense defaults for such a stack: lecun_normal kernels in layer order, biases stay zero."""
+    for kernel, _ in dense_views(flat, dims, off):
+        lecun_normal_(kernel, kernel.shape[0], generator)
+
+
 def as_generator(rng) -> torch.Generator:
     """The reference passes a jax PRNG key (train.py:47); here an int seed or a torch.Generator."""
     if isinstance(rng, torch.Generator):

@@ -12,9 +12,8 @@ second-order ("double backward") chain.  The spatial block — 94 % of the FLOPs
   precision="fp32" or any other shape: the generic dense GEMM path (exact fp32 / bf16 operands), layer by layer.
 """
 import ctypes
-from collections import OrderedDict
-from dataclasses import dataclass, field
-from typing import Any, Dict, List, Tuple
+from dataclasses import dataclass
+from typing import Dict, List, Optional, Tuple
 
 import torch
 
@@ -22,8 +21,8 @@ from . import _lib as L
 from . import _prof
 from . import _ws
 from . import ops
-from .model import ModelBase
-from .params import lecun_normal_
+from .model import ModelBase, nerf_trunk_bwd, nerf_trunk_dims, nerf_trunk_fwd, pack_buffer
+from .params import dense_spec, dense_views, init_dense_
 
 F32 = torch.float32
 HARMONIC_COUNTS = [1, 3, 5, 7, 9, 11, 13, 15]
@@ -46,6 +45,18 @@ def spherical_harmonic(sh_degree: int, coords: torch.Tensor) -> torch.Tensor:
     """Real spherical harmonics of normalized coords, [N x sh_degree^2] (ref_nerf.py:146-311)."""
     assert 1 <= sh_degree <= 8
     return ops.integrated_directional_encoding(sh_degree, coords.contiguous(), None)
+
+
+def aux_dict(aux2: torch.Tensor) -> Dict[str, torch.Tensor]:
+    """The [M, 2] aux columns of the head kernel as the aux dict of forward_points."""
+    return dict(normal_mse=aux2[:, 0], neg_normal=aux2[:, 1])
+
+
+def aux_grads(g_aux: Optional[Dict[str, torch.Tensor]], m: int, device) -> torch.Tensor:
+    """The gradient of the aux dict (None = zero) as the [M, 2] tensor the head backward reads."""
+    if g_aux is None:
+        return torch.zeros((m, 2), dtype=F32, device=device)
+    return torch.stack([g_aux["normal_mse"].reshape(-1), g_aux["neg_normal"].reshape(-1)], 1).contiguous()
 
 
 @dataclass
@@ -75,13 +86,6 @@ class RefNERFModel(RefNERFBase):
     # forward's plain bf16 operands
     render_precision: str = "bf16x3"
 
-    _pack_cache: Any = field(default=None, repr=False, compare=False)
-    _pack_generation: int = field(default=0, repr=False, compare=False)
-
-    def invalidate_packed(self) -> None:
-        """Call after the parameters were modified outside torch (e.g. by lnrf_adam_step)."""
-        self._pack_generation += 1
-
     def _use_fused_trunk(self) -> bool:
         return (self.precision == "bf16" and self.spatial_kernel == "fused"
                 and (self.input_layers, self.mid_layers, self.hidden_dim, self.x_freqs) == (5, 4, 256, 10))
@@ -92,64 +96,25 @@ class RefNERFModel(RefNERFBase):
 
     def packed_trunk(self, flat: torch.Tensor, kind: str = "bf16") -> torch.Tensor:
         """Fragment streams for the fused kernels ("bf16": trunk, normal pass and directional block, forward and transposed;
-        "split": hi/lo pairs of the forward-only streams for the render kernels); same cache discipline as
-        NeRFModel.packed_weights (fresh buffer per miss, entries keep their source tensor alive)."""
-        if self._pack_cache is None:
-            self._pack_cache = OrderedDict()
-        key = (kind, flat.data_ptr(), flat.numel(), flat._version, str(flat.device), self._pack_generation)
-        hit = self._pack_cache.get(key)
-        if hit is not None:
-            self._pack_cache.move_to_end(key)
-            return hit[1]
-        if kind == "split":
-            packed = torch.empty(L.lib().lnrf_refnerf_render_packed_bytes(), dtype=torch.uint8, device=flat.device)
-            L.check(L.lib().lnrf_refnerf_render_pack(L.ptr(flat), L.ptr(packed, torch.uint8), L.stream()),
-                    "refnerf_render_pack")
-        else:
-            packed = torch.empty(L.lib().lnrf_refnerf_trunk_packed_bytes(), dtype=torch.uint8, device=flat.device)
-            L.check(L.lib().lnrf_refnerf_trunk_pack(L.ptr(flat), L.ptr(packed, torch.uint8), L.stream()),
-                    "refnerf_trunk_pack")
-        self._pack_cache[key] = (flat, packed)
-        while len(self._pack_cache) > 6:
-            self._pack_cache.popitem(last=False)
-        return packed
+        "split": hi/lo pairs of the forward-only streams for the render kernels), cached by ModelBase._packed."""
+        lib = L.lib()
+        calls = ((lib.lnrf_refnerf_render_packed_bytes, lib.lnrf_refnerf_render_pack, "refnerf_render_pack")
+                 if kind == "split" else
+                 (lib.lnrf_refnerf_trunk_packed_bytes, lib.lnrf_refnerf_trunk_pack, "refnerf_trunk_pack"))
+        return self._packed(kind, flat, 6, lambda: pack_buffer(flat, *calls))
 
     def layer_dims(self) -> List[Tuple[int, int]]:
-        xe = 6 * self.x_freqs
-        dims, fan = [], xe
-        for _ in range(self.input_layers):
-            dims.append((fan, self.hidden_dim))
-            fan = self.hidden_dim
-        fan = self.hidden_dim + xe
-        for _ in range(self.mid_layers):
-            dims.append((fan, self.hidden_dim))
-            fan = self.hidden_dim
-        dims.append((self.hidden_dim + self.sh_degree ** 2 + 1, self.color_layer_dim))
-        dims.append((self.color_layer_dim, 3))
-        return dims
+        return nerf_trunk_dims(6 * self.x_freqs, self.input_layers, self.mid_layers, self.hidden_dim) + [
+            (self.hidden_dim + self.sh_degree ** 2 + 1, self.color_layer_dim), (self.color_layer_dim, 3)]
 
     def param_spec(self):
-        spec = []
-        for i, (fi, fo) in enumerate(self.layer_dims()):
-            spec.append((f"Dense_{i}", "kernel", (fi, fo)))
-            spec.append((f"Dense_{i}", "bias", (fo,)))
-        return spec
+        return dense_spec(self.layer_dims())
 
     def init_flat_(self, flat, gen):
-        off = 0
-        for fi, fo in self.layer_dims():
-            lecun_normal_(flat[off:off + fi * fo].view(fi, fo), fi, gen)
-            off += fi * fo + fo
+        init_dense_(flat, self.layer_dims(), gen)
 
     def _views(self, flat):
-        out, off = [], 0
-        for fi, fo in self.layer_dims():
-            k = flat[off:off + fi * fo].view(fi, fo)
-            off += fi * fo
-            b = flat[off:off + fo]
-            off += fo
-            out.append((k, b))
-        return out
+        return dense_views(flat, self.layer_dims())
 
     # ---- fused spatial block ---------------------------------------------------------------------------
     def _render_forward_points(self, flat, x, d):
@@ -175,7 +140,7 @@ class RefNERFModel(RefNERFBase):
             L.check(lib.lnrf_refnerf_dir_fwd_split(L.ptr(packed3, torch.uint8), L.ptr(dir_full), ld, m, L.ptr(dir_out),
                                                    L.stream()), "refnerf_dir_fwd_split")
             rgb = ops.refnerf_color_fwd(dir_out, spectral, diffuse)
-        return density, rgb, dict(normal_mse=aux2[:, 0], neg_normal=aux2[:, 1]), None
+        return density, rgb, aux_dict(aux2), None
 
     def _fused_forward_points(self, flat, x, d, save: bool):
         if self.render_precision not in ("bf16x3", "bf16"):
@@ -188,7 +153,7 @@ class RefNERFModel(RefNERFBase):
         ne = self.sh_degree ** 2
         ns = self.input_layers + self.mid_layers
         packed = self.packed_trunk(flat)
-        shape = L.NerfShape(5, 4, 256, 128, 10, 4)  # the trunk's buffers have NeRFModel's layout
+        shape = L.FUSED_NERF_SHAPE  # the trunk's buffers have NeRFModel's layout
         # GB-sized blocks are leased from step-persistent pools (_ws.py) and stay busy as long as the context lives
         leases = [_ws.lease("ref_save", lib.lnrf_nerf_save_bytes(ctypes.byref(shape), m), dev),
                   _ws.lease("ref_cdump", lib.lnrf_nerf_bwd_scratch_bytes(ctypes.byref(shape), m), dev)]
@@ -219,7 +184,7 @@ class RefNERFModel(RefNERFBase):
                 hcol = ops.dense_fwd(dir_in, W[ns][0], W[ns][1], L.ACT_RELU)
                 dir_out = ops.dense_fwd(hcol, W[ns + 1][0], W[ns + 1][1], L.ACT_NONE)
             rgb = ops.refnerf_color_fwd(dir_out, spectral, diffuse)
-        aux = dict(normal_mse=aux2[:, 0], neg_normal=aux2[:, 1])
+        aux = aux_dict(aux2)
         ctx = None
         if save:
             ctx = dict(kind="fused", flat=flat, packed=packed, x=x, d=d, save=save_buf, cdump=cdump, dir_in=dir_in,
@@ -235,10 +200,7 @@ class RefNERFModel(RefNERFBase):
         m, dev, hd = x.shape[0], grad_flat.device, self.hidden_dim
         ns = self.input_layers + self.mid_layers
         packed, save_buf, cdump = ctx["packed"], ctx["save"], ctx["cdump"]
-        if g_aux is None:
-            g_aux2 = torch.zeros((m, 2), dtype=F32, device=dev)
-        else:
-            g_aux2 = torch.stack([g_aux["normal_mse"].reshape(-1), g_aux["neg_normal"].reshape(-1)], 1).contiguous()
+        g_aux2 = aux_grads(g_aux, m, dev)
         with _prof.section(f"{self.tag}_head_bwd"), ops.dense_precision(self.precision):
             g_do, g_sp, g_df = ops.refnerf_color_bwd(ctx["dir_out"], ctx["spectral"], ctx["diffuse"],
                                                      g_rgb.reshape(-1, 3).contiguous())
@@ -257,7 +219,7 @@ class RefNERFModel(RefNERFBase):
                 g_dir_in = ops.dense_bwd_input(gy, W[ns][0], out=g_full[:, :dir_in.shape[1]])
             u = ops.refnerf_head_bwd(dir_in, ctx["nraw"], d, self.sh_degree, g_density.reshape(-1).contiguous(), g_df,
                                      g_sp, g_dir_in[:, hd:], g_aux2, g_dir_in)
-        shape = L.NerfShape(5, 4, 256, 128, 10, 4)
+        shape = L.FUSED_NERF_SHAPE
         with _prof.section(f"{self.tag}_spatial_bwd"):  # first-order: d L / d spatial_out -> Dense_8 .. Dense_0
             slease = _ws.lease("ref_scratch", lib.lnrf_refnerf_trunk_bwd_scratch_bytes(m), dev)
             scratch = slease.buf
@@ -290,22 +252,9 @@ class RefNERFModel(RefNERFBase):
         xe_w, ne = 6 * self.x_freqs, self.sh_degree ** 2
         ns = self.input_layers + self.mid_layers  # spatial Dense layers
         with _prof.section(f"{self.tag}_spatial_fwd"):
-            cat_x = torch.empty((m, hd + xe_w), dtype=F32, device=dev)
-            ops.sinusoidal_emb_into(x, self.x_freqs, cat_x, hd)
             dir_in = torch.empty((m, hd + ne + 1), dtype=F32, device=dev)  # [spatial_out, IDE, -d.n] (:63)
-            h = []  # relu outputs of Dense_0 .. Dense_{ns-2}; h[input_layers-1] aliases cat_x[:, :hd]
-            z = cat_x[:, hd:]
-            for i in range(self.input_layers):
-                out = cat_x[:, :hd] if i == self.input_layers - 1 else None
-                z = ops.dense_fwd(z, W[i][0], W[i][1], L.ACT_RELU, out=out)
-                h.append(z)
-            z = cat_x
-            for i in range(self.mid_layers):
-                last = i == self.mid_layers - 1
-                z = ops.dense_fwd(z, W[self.input_layers + i][0], W[self.input_layers + i][1],
-                                  L.ACT_NONE if last else L.ACT_RELU, out=dir_in[:, :hd] if last else None)
-                if not last:
-                    h.append(z)
+            cat_x, acts = nerf_trunk_fwd(W, x, self.x_freqs, self.input_layers, self.mid_layers, dir_in[:, :hd])
+            h = acts[:-1]  # relu outputs of Dense_0 .. Dense_{ns-2}; h[input_layers-1] aliases cat_x[:, :hd]
         with _prof.section(f"{self.tag}_normal_pass"):
             # analytic normal: c_l = d(-out0)/d y_l back to the embedding (ref_nerf.py:38-42)
             c = [None] * ns
@@ -329,7 +278,7 @@ class RefNERFModel(RefNERFBase):
             hcol = ops.dense_fwd(dir_in, W[ns][0], W[ns][1], L.ACT_RELU)  # ref_nerf.py:105-107
             dir_out = ops.dense_fwd(hcol, W[ns + 1][0], W[ns + 1][1], L.ACT_NONE)
             rgb = ops.refnerf_color_fwd(dir_out, spectral, diffuse)
-        aux = dict(normal_mse=aux2[:, 0], neg_normal=aux2[:, 1])
+        aux = aux_dict(aux2)
         ctx = None
         if save:
             ctx = dict(flat=flat, x=x, d=d, cat_x=cat_x, dir_in=dir_in, h=h, c=c, nraw=nraw, density=density,
@@ -345,10 +294,7 @@ class RefNERFModel(RefNERFBase):
         m, dev, hd = x.shape[0], grad_flat.device, self.hidden_dim
         xe_w = 6 * self.x_freqs
         ns, il = self.input_layers + self.mid_layers, self.input_layers
-        if g_aux is None:
-            g_aux2 = torch.zeros((m, 2), dtype=F32, device=dev)
-        else:
-            g_aux2 = torch.stack([g_aux["normal_mse"].reshape(-1), g_aux["neg_normal"].reshape(-1)], 1).contiguous()
+        g_aux2 = aux_grads(g_aux, m, dev)
         with _prof.section(f"{self.tag}_head_bwd"):
             g_do, g_sp, g_df = ops.refnerf_color_bwd(ctx["dir_out"], ctx["spectral"], ctx["diffuse"],
                                                      g_rgb.reshape(-1, 3).contiguous())
@@ -360,12 +306,7 @@ class RefNERFModel(RefNERFBase):
                                      g_sp, g_dir_in[:, hd:], g_aux2, g_dir_in)
         with _prof.section(f"{self.tag}_spatial_bwd"):
             # (i) first-order path: d L / d spatial_out back through Dense_{ns-1} .. Dense_0
-            gy = g_dir_in[:, :hd]  # Dense_{ns-1} output is linear
-            for l in range(ns - 1, -1, -1):
-                inp = cat_x if l == il else (cat_x[:, hd:] if l == 0 else h[l - 1])
-                ops.dense_bwd_weight(inp, gy, G[l][0], G[l][1])
-                if l > 0:
-                    gy = ops.dense_bwd_input(gy, W[l][0][:hd], gate=h[l - 1])
+            nerf_trunk_bwd(W, G, cat_x, h, il, self.mid_layers, g_dir_in[:, :hd])  # Dense_{ns-1} output is linear
         with _prof.section(f"{self.tag}_normal_bwd"):
             # (ii) second-order path: the normal pass is a chain in the SAME kernels with the ReLU masks
             # fixed (ReLU'' = 0 a.e.): ge = W_0 c_0 + W_5[hd:] c_5, c_{l-1} = mask_{l-1} * (W_l c_l).

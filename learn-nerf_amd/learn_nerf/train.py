@@ -144,13 +144,9 @@ class TrainLoop:
     def load(self, path: str, load_optimizer: bool = True):
         """Load parameters (and, when present, the optimiser state) from a file written by save()."""
         with np.load(path, allow_pickle=False) as blob:
-            if str(blob["format"]) != "lnrf-params-v3":
-                raise ValueError(f"{path}: not an lnrf-params-v3 checkpoint")
             c, f, bg = self._slices(self.flat)
             for name, model, dst in (("coarse", self.coarse, c), ("fine", self.fine, f)):
-                leaves = [torch.from_numpy(blob[f"{name}/{module}/{leaf}"]).to(F32).reshape(-1)
-                          for module, leaf, _ in model.param_spec()]
-                dst.copy_(torch.cat(leaves).to(self.device))
+                dst.copy_(_checkpoint_flat(blob, path, name, model).to(self.device))
             bg.copy_(torch.from_numpy(blob["background"]).to(F32).to(self.device))
             if load_optimizer and "opt/m" in blob and blob["opt/m"].shape[0] == self.flat.numel():
                 self.state.opt_m.copy_(torch.from_numpy(blob["opt/m"]).to(self.device))
@@ -359,14 +355,19 @@ def load_params(path: str, coarse: ModelBase, fine: ModelBase, device) -> Dict[s
     (what scripts/render_nerf.py:56-58 gets from pickle.load in the reference)."""
     out = {}
     with np.load(path, allow_pickle=False) as blob:
-        if str(blob["format"]) != "lnrf-params-v3":
-            raise ValueError(f"{path}: not an lnrf-params-v3 checkpoint")
         for name, model in (("coarse", coarse), ("fine", fine)):
-            leaves = [torch.from_numpy(blob[f"{name}/{module}/{leaf}"]).to(F32).reshape(-1)
-                      for module, leaf, _ in model.param_spec()]
-            out[name] = model.tree(torch.cat(leaves).to(device))
+            out[name] = model.tree(_checkpoint_flat(blob, path, name, model).to(device))
         out["background"] = torch.from_numpy(blob["background"]).to(F32).to(device)
     return out
+
+
+def _checkpoint_flat(blob, path: str, name: str, model: ModelBase) -> torch.Tensor:
+    """The parameters of model `name` ("coarse" | "fine") in the open archive of a checkpoint written by TrainLoop.save,
+    as one flat fp32 host tensor in param_spec order."""
+    if str(blob["format"]) != "lnrf-params-v3":
+        raise ValueError(f"{path}: not an lnrf-params-v3 checkpoint")
+    return torch.cat([torch.from_numpy(blob[f"{name}/{module}/{leaf}"]).to(F32).reshape(-1)
+                      for module, leaf, _ in model.param_spec()])
 
 
 def _flatten_tree(tree, prefix=""):

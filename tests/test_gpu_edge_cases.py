@@ -121,6 +121,46 @@ def test_non_default_nerf_shape_uses_dense_path():
     assert (rgb16.cpu().double() - rr).abs().max().item() > 1e-5
 
 
+@pytest.mark.parametrize("input_layers,mid_layers", [(1, 2), (2, 1)])
+def test_single_layer_trunk_blocks_on_the_dense_path(input_layers, mid_layers):
+    """The edge shapes of the trunk on the exact dense path, forward and backward: with input_layers=1 the layer that writes
+    into the skip concat is also the first layer, with mid_layers=1 the layer that reads the concat also writes the head's
+    input.  Tolerances of the default shape's comparisons (test_gpu_nerf_mlp.py: 2e-5 forward, 1e-5 relative L2 per leaf
+    at m <= 100)."""
+    from learn_nerf.model import NeRFModel
+    from oracle import model as OM
+
+    kw = dict(input_layers=input_layers, mid_layers=mid_layers, hidden_dim=32, color_layer_dim=16, x_freqs=2, d_freqs=2)
+    m = 33
+    model = NeRFModel(precision="fp32", **kw)
+    flat = model.flat(model.init(dict(params=0))["params"])
+    gen = torch.Generator().manual_seed(1)
+    off = 0
+    for fi, fo in model.layer_dims():  # non-zero biases
+        off += fi * fo
+        flat[off:off + fo] += (torch.randn(fo, generator=gen) * 0.1).cuda()
+        off += fo
+    x = (torch.rand(m, 3, generator=gen) * 2 - 1).float()
+    d = torch.randn(m, 3, generator=gen).float()
+    g_dens = torch.randn(m, generator=gen).float()
+    g_rgb = torch.randn(m, 3, generator=gen).float()
+    dens, rgb, _, ctx = model.forward_points(flat, x.cuda(), d.cuda(), save=True)
+    grad = torch.zeros_like(flat)
+    model.backward(ctx, g_dens.cuda(), g_rgb.cuda(), None, grad)
+    p = flat.cpu().double().requires_grad_(True)
+    rd, rr, _ = OM.nerf_mlp(p, x.double(), d.double(), **kw)
+    assert (rgb.cpu().double() - rr).abs().max().item() < 2e-5
+    assert torch.allclose(dens.cpu().double(), rd[:, 0], atol=2e-5, rtol=2e-5)
+    (ref,) = torch.autograd.grad((rd[:, 0] * g_dens.double()).sum() + (rr * g_rgb.double()).sum(), p)
+    got, off = grad.cpu().double(), 0
+    for i, (fi, fo) in enumerate(model.layer_dims()):
+        for name, n in (("kernel", fi * fo), ("bias", fo)):
+            rel = ((got[off:off + n] - ref[off:off + n]).norm() / (ref[off:off + n].norm() + 1e-30)).item()
+            print(f"Dense_{i}.{name}: rel L2 err {rel:.3e}")
+            assert rel < 1e-5, (i, name, rel)
+            off += n
+
+
 def test_cpu_tensor_is_rejected_loudly():
     from learn_nerf import ops
 

@@ -77,14 +77,22 @@ def make_model(seed=3, precision="fp32", **kw):
     return model, params, flat
 
 
-@pytest.mark.parametrize("kw,m", [(dict(), 600), (dict(hidden_dim=64, color_layer_dim=32, sh_degree=3), 1500)])
+# the last two: input_layers=1 (the layer that writes into the skip concat is also the first one; the second-order chain's
+# il == 1 branch) and mid_layers=1 (the layer that reads the concat also writes the head's input)
+SMALL = dict(hidden_dim=32, color_layer_dim=16, x_freqs=2, d_freqs=2, sh_degree=2)
+
+
+@pytest.mark.parametrize("kw,m", [(dict(), 600), (dict(hidden_dim=64, color_layer_dim=32, sh_degree=3), 1500),
+                                  (dict(input_layers=1, mid_layers=2, **SMALL), 33),
+                                  (dict(input_layers=2, mid_layers=1, **SMALL), 33)])
 def test_ref_nerf_forward_backward(kw, m):
     model, params, flat = make_model(**kw)
     gen = torch.Generator().manual_seed(5)
     x = (torch.rand(m, 3, generator=gen) * 2 - 1).float()
     d = unit(m, seed=9)
     dens, rgb, aux = model.apply(dict(params=params), x.cuda(), d.cuda())
-    okw = dict(sh_degree=model.sh_degree, hidden_dim=model.hidden_dim, color_layer_dim=model.color_layer_dim)
+    okw = dict(sh_degree=model.sh_degree, hidden_dim=model.hidden_dim, color_layer_dim=model.color_layer_dim,
+               input_layers=model.input_layers, mid_layers=model.mid_layers, x_freqs=model.x_freqs)
     f64 = flat.cpu().double().requires_grad_(True)
     rd, rr, raux = ORF.ref_nerf_model(f64, x.double(), d.double(), **okw)
     assert dens.shape == (m, 1) and set(aux) == {"normal_mse", "neg_normal"}
