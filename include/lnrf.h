@@ -233,9 +233,9 @@ int lnrf_hashgrid_fwd(const lnrf_hashgrid_desc* desc, const float* tables, const
                       float* enc_t, lnrf_stream_t stream);
 
 /* g_tables += scatter of g_enc_t (same layout as enc_t) through the same indices/weights, with caller-provided
- * scratch (lnrf_hashgrid_bwd_scratch_bytes): hashed levels are reduced
- * without global float atomics (bin by 8K-entry table slice, then one workgroup per bucket accumulates in
- * LDS).  u == NULL: value weights (first-order gradient); u [M,3]: derivative weights (see bwd_dir).
+ * scratch (lnrf_hashgrid_bwd_scratch_bytes): every level of at most 256 4096-entry table slices, hashed or dense, is
+ * reduced without global float atomics (bin by 4096-entry slice, then one workgroup per bucket, several for a large
+ * one, accumulates in LDS).  u == NULL: value weights (first-order gradient); u [M,3]: derivative weights (see bwd_dir).
  * level_absmax (optional, u == NULL only): n_levels floats, level_absmax[l] >= max |g_enc_t rows 2l, 2l+1|;
  * lnrf_ngp_mlp_bwd produces it while writing g_enc_t.  WITH it the contributions are binned as 26-bit fixed point of
  * that bound (8-byte tuples: resolution 2^-25 of the level's bound per contribution — a QUANTISED scatter, the fused
@@ -243,7 +243,8 @@ int lnrf_hashgrid_fwd(const lnrf_hashgrid_desc* desc, const float* tables, const
  * binning and the reduce pass sums in 64-bit fixed point at 2^-46 of it per contribution — the exact-fp32 path's
  * scatter (instant_ngp.py:211-224 under jax.grad).  Either way NaN / Inf contributions reach the table through float
  * atomics, as a floating-point scatter-add would propagate them.
- * scratch == NULL falls back to the LDS-sliced / atomic kernels. */
+ * scratch == NULL, and a larger table, fall back to float atomics (pre-reduced in LDS for tables of up to 64 8192-entry
+ * slices, except a hashed table of one). */
 int64_t lnrf_hashgrid_bwd_scratch_bytes(const lnrf_hashgrid_desc* desc, int64_t m);
 int lnrf_hashgrid_bwd_bucketed(const lnrf_hashgrid_desc* desc, const float* x, const float* u, int64_t m,
                                const float* g_enc_t, const float* level_absmax, float* g_tables, void* scratch,

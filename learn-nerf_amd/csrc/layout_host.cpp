@@ -2,11 +2,14 @@
 // positional-encoding sincos (fast_math.h), so that tests/test_nerf_layout.py can run the exact packing /
 // fragment logic on the CPU (no GPU needed) with an MFMA emulator; and of the weight-gradient problem lists and their
 // gradient-vector addressing (nerf_wgrad.h); and of the tables and pack walks of the fused InstantNGPModel MLP (ngp_layout.h);
-// and of the dispatch plan and tile map of the generic dense GEMM (dense_plan.h, tests/test_dense_plan.py).
+// and of the dispatch plan and tile map of the generic dense GEMM (dense_plan.h, tests/test_dense_plan.py); and of the
+// cell geometry, launch plans and scratch layout of the hash grid (hashgrid_plan.h, tests/test_hashgrid_plan.py).
 #include <stdint.h>
+#include <string.h>
 
 #include "dense_plan.h"
 #include "fast_math.h"
+#include "hashgrid_plan.h"
 #include "nerf_wgrad.h"
 #include "ngp_layout.h"
 
@@ -78,6 +81,11 @@ static int64_t ngp_count_owners(const NgpWgradProblem& pb, int64_t dense_off, in
   return outside;
 }
 static bool ngp_enc_dim_ok(int enc_dim) { return enc_dim >= 1 && enc_dim <= 32; }
+static HashGridDesc hashgrid_desc_of(const void* desc) {
+  HashGridDesc d;
+  memcpy(&d, desc, sizeof(d));
+  return d;
+}
 
 extern "C" {
 int lnrf_host_fwd_frags(void) { return kFwdFrags; }
@@ -254,6 +262,67 @@ void lnrf_host_gemm_tile(int64_t I, int32_t J, uint32_t block0, int64_t count, i
 // the scratch sizes behind lnrf_dense_bwd_weight_scratch_bytes / lnrf_gemm_f32_det_scratch_bytes
 int64_t lnrf_host_dense_bwd_weight_scratch_bytes(int64_t m, int32_t k, int32_t n) { return dense_wgrad_scratch_bytes(m, k, n); }
 int64_t lnrf_host_gemm_det_scratch_bytes(int64_t I, int32_t J, int64_t R) { return gemm_det_scratch_bytes(I, J, R); }
+// ---- hash grid (hashgrid_plan.h); desc is a lnrf_hashgrid_desc ----
+// the 8 corners of point x at `level` in the kernels' order (xo outermost): table entry, weight, d weight / d x
+void lnrf_host_hashgrid_corners(const void* desc, int32_t level, const float* x, uint32_t* idx, float* w, float* dw) {
+  const HashGridDesc d = hashgrid_desc_of(desc);
+  const int G = d.grid_size[level];
+  const Corner k = locate(x, d, G);
+  for (int c = 0; c < 8; ++c) {
+    const int xo = c >> 2, yo = (c >> 1) & 1, zo = c & 1;
+    idx[c] = entry_index(k.base[0] + xo, k.base[1] + yo, k.base[2] + zo, G, d.table_size[level], d.hashed[level]);
+    w[c] = corner_weight(k, xo, yo, zo);
+    corner_weight_grad(k, xo, yo, zo, dw + 3 * c);
+  }
+}
+// XCD plan of hashgrid_fwd_xcd_kernel for `n` levels and m samples.  Returns the grid (0: inconsistent plan);
+// plan[0..8] = first_seg, then n_segs x (level, first chunk, chunks) from plan[9]; work[2 b], work[2 b + 1] = level (-1:
+// nothing) and first sample of workgroup b.  plan / work == NULL: not written.
+int64_t lnrf_host_hashgrid_xcd_plan(const void* desc, const int32_t* levels, int32_t n, int64_t m, int32_t* plan,
+                                    int64_t* work) {
+  const HashGridDesc d = hashgrid_desc_of(desc);
+  LevelList ll;
+  ll.n = n;
+  for (int i = 0; i < n; ++i) ll.level[i] = levels[i];
+  unsigned grid = 0;
+  const XcdPlan p = make_xcd_plan(d, ll, m, &grid);
+  for (int x = 0; plan && x <= kXcds; ++x) plan[x] = p.first_seg[x];
+  for (int s = 0; plan && s < p.n_segs; ++s) {
+    plan[9 + 3 * s] = p.seg_level[s]; plan[10 + 3 * s] = p.seg_chunk0[s]; plan[11 + 3 * s] = p.seg_chunks[s];
+  }
+  for (unsigned b = 0; work && b < grid; ++b) {
+    const XcdWork w = xcd_work(p, b);
+    work[2 * b] = w.seg < 0 ? -1 : xcd_level(p, w);
+    work[2 * b + 1] = w.seg < 0 ? 0 : xcd_first_sample(p, w);
+  }
+  return grid;
+}
+// Bucket plan of the scatter for m samples.  Returns the bucketed levels n; levels[7 i ..] = level, slices, split, first
+// reduce workgroup, first tuple, first cursor, capacity; scratch[0..4] = cursor bytes, byte offsets of the level maxima
+// and of the tuples, total bytes, reduce workgroups.
+int32_t lnrf_host_hashgrid_bucket_plan(const void* desc, int64_t m, int64_t* levels, int64_t* scratch) {
+  const BucketPlan p = make_plan(hashgrid_desc_of(desc), m);
+  for (int i = 0; i < p.n; ++i) {
+    const int64_t v[7] = {p.level[i], p.slices[i], p.split[i], p.wg_off[i], p.tuple_off[i], p.cursor_off[i], p.cap[i]};
+    for (int j = 0; j < 7; ++j) levels[7 * i + j] = v[j];
+  }
+  const BucketScratch s = bucket_scratch(p);
+  scratch[0] = s.cursor_bytes; scratch[1] = s.level_max_off; scratch[2] = s.tuple_off; scratch[3] = s.total;
+  scratch[4] = p.wg_off[p.n];
+  return p.n;
+}
+// reduce workgroups block0 .. block0 + count - 1 of that plan, each for a bucket holding `tuples` tuples:
+// out[6 e ..] = entry of the plan, its level, bucket, part, first and one-past-last tuple the workgroup reads
+void lnrf_host_hashgrid_reduce_work(const void* desc, int64_t m, int32_t block0, int64_t count, int64_t tuples,
+                                    int64_t* out) {
+  const BucketPlan p = make_plan(hashgrid_desc_of(desc), m);
+  for (int64_t e = 0; e < count; ++e) {
+    const ReduceWork w = reduce_work(p, block0 + (int)e);
+    const TupleRange r = reduce_range(p, w, tuples);
+    const int64_t v[6] = {w.li, w.level, w.bucket, w.part, r.lo, r.hi};
+    for (int j = 0; j < 6; ++j) out[6 * e + j] = v[j];
+  }
+}
 int64_t lnrf_host_wgrad_owners(int which, int64_t n_tiles, int32_t* count, int64_t n) {
   const WgradList list = wgrad_list_of(which, n_tiles);
   int64_t outside = 0;

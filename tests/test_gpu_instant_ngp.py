@@ -387,8 +387,9 @@ def test_ngp_ref_nerf_forward_backward(levels, table):
 
 @pytest.mark.parametrize("clustered", [False, True])
 def test_bucketed_scatter_matches_direct_path(clustered):
-    """Levels with 4..128 table slices (dense 32^3 / 48^3 and hashed 128^3 / 512^3 here) use the bucketed
-    reduction; same result as the LDS-sliced / atomic kernels, for value weights and for derivative weights.
+    """With scratch every level here is bucketed (at most 256 4096-entry slices: dense 16^3, 32^3, 48^3 with 1, 8 and 27,
+    hashed 128^3 / 512^3 with 32); same result as the fallback kernel that runs without scratch (16^3 whole in LDS, the
+    others in LDS by 8192-entry slice), for value weights and for derivative weights.
     clustered: all samples in 2 % of the box, so the dense levels overflow their bucket capacity and exercise
     the atomic fallback of the bin kernel."""
     import ctypes
