@@ -322,7 +322,9 @@ __global__ void composite_bwd_kernel(const float* __restrict__ ts, const float* 
 }
 
 // g_background[c] += sum over blocks of parts[block][c], c < 3: thread t adds the rows t, t + 256, ... in order, then the
-// 256 partial sums meet in a fixed binary tree
+// 256 partial sums meet in a fixed binary tree.  The last add is atomic: the coarse pass (second stream) and the fine pass
+// of one step fold into the same three words and no event orders them; two addends into a zeroed word commute exactly, so
+// the step stays bit-reproducible
 __global__ __launch_bounds__(256) void composite_bg_fold_kernel(const float* __restrict__ parts, int n_blocks,
                                                                 float* __restrict__ g_background) {
   __shared__ float red[256][3];
@@ -341,7 +343,7 @@ __global__ __launch_bounds__(256) void composite_bg_fold_kernel(const float* __r
     }
     __syncthreads();
   }
-  if (threadIdx.x < 3) g_background[threadIdx.x] += red[0][threadIdx.x];
+  if (threadIdx.x < 3) atomicAdd(g_background + threadIdx.x, red[0][threadIdx.x]);
 }
 
 // fine_sampling (render.py:211-257). One wave per ray; LDS per wave: xs[tc+1], ys[tc+1],

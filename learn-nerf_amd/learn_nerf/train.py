@@ -97,7 +97,9 @@ class TrainLoop:
         # render.py:211-257), so it runs on a second HIP stream beside the fine forward / backward and is joined
         # before the optimizer (measured: Ref-NeRF 11.03 -> 10.79 ms per step; NeRFModel and the hash-grid model opt
         # out through overlap_backward_hint: 5.015 -> 5.002 ms is within noise and doubles the per-kernel timings,
-        # hash grid 2.30 -> 2.33 ms).  LNRF_OVERLAP_BACKWARD=0 / 1 overrides.
+        # hash grid 2.30 -> 2.33 ms).  LNRF_OVERLAP_BACKWARD=0 / 1 overrides.  The model slices of the two passes are
+        # disjoint; the three words they share, the background gradient, are added to atomically
+        # (composite_bg_fold_kernel), and two addends into a zeroed word give the same bits in either order.
         env = os.environ.get("LNRF_OVERLAP_BACKWARD")
         want = (env != "0") if env is not None else bool(getattr(coarse, "overlap_backward_hint", True))
         self.overlap_backward = torch.device(self.device).type == "cuda" and coarse is not fine and want
@@ -254,8 +256,10 @@ class TrainLoop:
                                                                        gslice if want_grad else None)
         return loss_dict, world
 
-    def _average_density(self, key, model, pflat, bmin, bmax, gslice):
-        """TrainLoop.average_density (train.py:167-184): mean density at random bbox points."""
+    def density_points(self, key, bmin, bmax):
+        """The points of TrainLoop.average_density (train.py:167-176) for a key and box: coords[B,3] uniform in the box and
+        unit dirs[B,3], B = density_penalty_batch_size.  A function of the key alone, so the coarse and the fine model of
+        one step (both called with density_key, train.py:153-163) are penalised at the same points."""
         b = self.density_penalty_batch_size
         k = as_key(key)
         gen = torch.Generator(device=self.device)
@@ -265,8 +269,13 @@ class TrainLoop:
         coords = torch.rand((b, 3), generator=gen, device=self.device) * (hi - lo) + lo
         dirs = torch.randn((b, 3), generator=gen, device=self.device)
         dirs = dirs / dirs.norm(dim=-1, keepdim=True)
-        dens, rgb, aux, ctx = model.forward_points(pflat, coords.contiguous(), dirs.contiguous(),
-                                                   save=gslice is not None)
+        return coords.contiguous(), dirs.contiguous()
+
+    def _average_density(self, key, model, pflat, bmin, bmax, gslice):
+        """TrainLoop.average_density (train.py:167-184): mean density at random bbox points."""
+        b = self.density_penalty_batch_size
+        coords, dirs = self.density_points(key, bmin, bmax)
+        dens, rgb, aux, ctx = model.forward_points(pflat, coords, dirs, save=gslice is not None)
         if gslice is not None:
             g_d = torch.full_like(dens, self.density_penalty / b)
             g_aux = {kk: torch.zeros_like(v) for kk, v in aux.items()} if aux else None

@@ -9,44 +9,11 @@ from oracle import model as OM
 from oracle import philox
 from oracle import render as OR
 from oracle import train as OT
+from train_step_reference import boost_density, make_batch, split_flat, uniforms_for
 
 pytestmark = pytest.mark.gpu
 F64 = torch.float64
 BMIN, BMAX = (-1.0, -1.0, -1.0), (1.0, 1.0, 1.0)
-
-
-def make_batch(n, seed=0):
-    gen = torch.Generator().manual_seed(seed)
-    o = torch.randn(n, 3, generator=gen)
-    o = 4 * o / o.norm(dim=-1, keepdim=True)
-    d = -o + (torch.rand(n, 3, generator=gen) - 0.5) * 0.6
-    d[: n // 10] = torch.randn(n // 10, 3, generator=gen)  # some rays miss the box
-    d = d / d.norm(dim=-1, keepdim=True)
-    c = torch.rand(n, 3, generator=gen) * 2 - 1
-    return torch.stack([o, d, c], 1).float().contiguous()
-
-
-def boost_density(loop):
-    """Random-init NeRF predicts softplus(~0): scale the density head so alpha spans (0,1)."""
-    for name in ("coarse", "fine"):
-        p = loop.state.params[name]
-        p["Dense_9"]["kernel"].mul_(6.0)
-        p["Dense_9"]["bias"].add_(1.5)
-
-
-def uniforms_for(key_seed, n, tc, tf):
-    from learn_nerf.rng import Key, split
-
-    render_key, _ = split(Key(key_seed), 2)
-    ck, fk = split(render_key, 2)
-    uc = torch.from_numpy(philox.ray_uniforms(ck.seed, 0, 0, n, tc))
-    uf = torch.from_numpy(philox.ray_uniforms(fk.seed, 1, 0, n, tf))
-    return uc, uf
-
-
-def split_flat(loop):
-    c, f, bg = loop._slices(loop.flat)
-    return c.cpu().double(), f.cpu().double(), bg.cpu().double()
 
 
 def _models(mode):
