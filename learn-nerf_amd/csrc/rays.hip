@@ -646,6 +646,9 @@ extern "C" int lnrf_fine_sample(const float* ts_c, const float* t_min, const flo
   if (tf == 0 && !combine) return LNRF_OK;
   const int wpb = 4;
   const size_t lds = (size_t)wpb * (2 * (tc + 1) + tc + tf) * sizeof(float);
+  // 160 KiB is one CU's whole LDS.  Observed on an MI355X (tests/test_gpu_rays_edges.py): launches with 65,536 B,
+  // 65,552 B and 163,840 B of dynamic LDS all succeed and give correct samples without a
+  // hipFuncSetAttribute(max dynamic LDS) call first, so this launch makes none
   LNRF_CHECK_ARG(lds <= 160 * 1024, "tc+tf too large for LDS");
   hipLaunchKernelGGL(fine_sample_kernel, dim3((unsigned)((n_rays + wpb - 1) / wpb)), dim3(wpb * 64),
                      lds, as_stream(stream), ts_c, t_min, t_max, density_c, n_rays, tc, tf, eps,
