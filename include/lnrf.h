@@ -717,6 +717,36 @@ int lnrf_compact_mask(const uint8_t* mask, int64_t n, int32_t* idx, int64_t* cou
 int lnrf_scatter_rows(const float* src, int32_t row_floats, const int32_t* idx, int64_t n, float* out, int64_t n_out,
                       lnrf_stream_t stream);
 
+/* ---------------------------------------------------- connected components ---- */
+
+/* Connected components of a 3-D mask (additive; csrc/components.hip, whose header comment fixes the conventions and
+ * names the passes; learn_nerf/components.py runs the rounds).  mask: uint8 [nx, ny, nz], non-zero = foreground, linear
+ * index (i*ny + j)*nz + k, every dimension >= 1 (LNRF_ERR_ARG) and N = nx*ny*nz <= INT32_MAX (LNRF_ERR_UNSUPPORTED,
+ * scratch bytes -1; checked before any pointer is looked at).  connectivity: 6 or 26 (LNRF_ERR_ARG otherwise).
+ * labels: int32 [N], the smallest linear index of the cell's component, -1 for background.
+ * scratch: lnrf_cc_scratch_bytes(nx, ny, nz) bytes, 4-byte aligned, the same block for lnrf_cc_local and every
+ * lnrf_cc_merge_round of one labelling; every byte that is read is written first. */
+#define LNRF_CC_MAX_ROUNDS 64
+int32_t lnrf_cc_max_rounds(void); /* (host) LNRF_CC_MAX_ROUNDS */
+int64_t lnrf_cc_scratch_bytes(int64_t nx, int64_t ny, int64_t nz);
+/* init + per-tile pass: labels = the smallest index of the cell's component WITHIN its 8^3 tile. */
+int lnrf_cc_local(const uint8_t* mask, int64_t nx, int64_t ny, int64_t nz, int32_t connectivity, int32_t* labels,
+                  void* scratch, int64_t scratch_bytes, lnrf_stream_t stream);
+/* One merge round (merge across all neighbours + flatten) on the labels and scratch of lnrf_cc_local.  changed: one
+ * device int32, cleared first and set to 1 when the round lowered a parent or a bounded walk gave up; the host reads it
+ * back, and the labels are final after the first round that leaves 0 — not before.  round: 0, 1, ... as counted by the
+ * caller; round >= LNRF_CC_MAX_ROUNDS launches nothing and returns LNRF_ERR_UNSUPPORTED ("no fixed point"). */
+int lnrf_cc_merge_round(int64_t nx, int64_t ny, int64_t nz, int32_t connectivity, int32_t round, int32_t* labels,
+                        int32_t* changed, void* scratch, int64_t scratch_bytes, lnrf_stream_t stream);
+/* sizes int32 [n]: the number of cells labelled r at index r, 0 elsewhere (integer atomics: exact).  Labels outside
+ * [0, n) count nowhere.  1 <= n <= INT32_MAX. */
+int lnrf_cc_sizes(const int32_t* labels, int64_t n, int32_t* sizes, lnrf_stream_t stream);
+/* keep uint8 [n]: 1 iff labels[c] >= 0, s = sizes[labels[c]] >= min_cells (>= 1) and (s > cut_size or (s == cut_size
+ * and labels[c] <= cut_label)): (cut_size, cut_label) is the last component kept in the order (size descending, label
+ * ascending), which the host finds from sizes; cut_size = 0 keeps every component of min_cells or more. */
+int lnrf_cc_keep(const int32_t* labels, const int32_t* sizes, int64_t n, int32_t min_cells, int32_t cut_size,
+                 int32_t cut_label, uint8_t* keep, lnrf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

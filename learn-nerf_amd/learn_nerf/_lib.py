@@ -179,6 +179,12 @@ PROTOTYPES = {
                                      _P, _P, _P]),
     "lnrf_compact_mask": (c_int32, [_P, c_int64, _P, _P, _P]),
     "lnrf_scatter_rows": (c_int32, [_P, c_int32, _P, c_int64, _P, c_int64, _P]),
+    "lnrf_cc_max_rounds": (c_int32, []),
+    "lnrf_cc_scratch_bytes": (c_int64, [c_int64, c_int64, c_int64]),
+    "lnrf_cc_local": (c_int32, [_P, c_int64, c_int64, c_int64, c_int32, _P, _P, c_int64, _P]),
+    "lnrf_cc_merge_round": (c_int32, [c_int64, c_int64, c_int64, c_int32, c_int32, _P, _P, _P, c_int64, _P]),
+    "lnrf_cc_sizes": (c_int32, [_P, c_int64, _P, _P]),
+    "lnrf_cc_keep": (c_int32, [_P, _P, c_int64, c_int32, c_int32, c_int32, _P, _P]),
 }
 
 _lib = None

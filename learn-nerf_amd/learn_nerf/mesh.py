@@ -89,17 +89,40 @@ def marching_cubes(volume: torch.Tensor, level: float) -> Tuple[torch.Tensor, to
     return verts, faces
 
 
-def extract_mesh(model, params, bbox_min, bbox_max, resolution: int, batch_size: int,
-                 threshold: float) -> Tuple[torch.Tensor, torch.Tensor, float]:
+def filter_occupancy(occupancy: torch.Tensor, threshold: float, min_component: int = 1, keep_largest: int = None,
+                     connectivity: int = 26) -> Tuple[torch.Tensor, dict]:
+    """
+    Floater removal on an occupancy volume [nx, ny, nz] (additive; learn_nerf/components.py): the foreground is
+    occupancy > threshold, marching cubes' "inside" (so NaN is background); the points of every component smaller than
+    `min_component` points or, with `keep_largest`, beyond the largest `keep_largest` components are set to 0, every
+    other point keeps its value.  -> (filtered copy, info of keep_components).
+    """
+    from .components import keep_components
+
+    inside = occupancy > threshold
+    keep, info = keep_components(inside, min_cells=min_component, keep_largest=keep_largest, connectivity=connectivity)
+    return occupancy.masked_fill(inside & (keep == 0), 0.0), info
+
+
+def extract_mesh(model, params, bbox_min, bbox_max, resolution: int, batch_size: int, threshold: float,
+                 min_component: int = 1, keep_largest: int = None, connectivity: int = 26,
+                 info: dict = None) -> Tuple[torch.Tensor, torch.Tensor, float]:
     """
     scripts/marching_cubes.py:38-66: occupancy 1 - exp(-sigma) (fp32) on the grid, one layer of zero padding, marching
     cubes at `threshold`.  -> (verts [V, 3] in padded index space, faces [F, 3], largest occupancy of the grid).
+    Additive: with min_component > 1 or keep_largest the volume goes through filter_occupancy first, whose info is
+    copied into `info` when one is given; with the defaults no component kernel runs.
     """
     sigma = density_grid(model, params, bbox_min, bbox_max, resolution, batch_size)
     occupancy = 1 - torch.exp(-sigma)
+    largest = float(occupancy.max())
+    if min_component != 1 or keep_largest is not None:
+        occupancy, found = filter_occupancy(occupancy, threshold, min_component, keep_largest, connectivity)
+        if info is not None:
+            info.update(found)
     padded = F.pad(occupancy, (1, 1, 1, 1, 1, 1), mode="constant", value=0.0)
     verts, faces = marching_cubes(padded, threshold)
-    return verts, faces, float(occupancy.max())
+    return verts, faces, largest
 
 
 def reference_frame(verts, faces, bbox_min, bbox_max, resolution: int) -> Tuple[np.ndarray, np.ndarray]:

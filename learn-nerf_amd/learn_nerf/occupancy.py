@@ -9,8 +9,8 @@ can sit between the corners.  The dilation and the low default threshold make a 
 is an approximation the user opts into, and the renderer without a grid stays the yardstick.
 """
 import math
-from dataclasses import dataclass
-from typing import Any, Tuple
+from dataclasses import dataclass, replace
+from typing import Any, Optional, Tuple
 
 import torch
 
@@ -52,24 +52,58 @@ class OccupancyGrid:
 
     @classmethod
     def from_model(cls, model, params, bbox_min, bbox_max, resolution: int, threshold: float = 0.01,
-                   dilate: int = 1, batch_size: int = 1 << 18) -> "OccupancyGrid":
+                   dilate: int = 1, batch_size: int = 1 << 18, min_cells: int = 1, keep_largest: Optional[int] = None,
+                   connectivity: int = 26) -> "OccupancyGrid":
         """Evaluate `model` at the (resolution + 1)^3 cell corners (direction d = 0) and build the grid: a cell is
         occupied when a corner of it, or of a cell within `dilate` cells (Chebyshev), reaches the density whose
-        opacity over one cell diagonal is `threshold`."""
+        opacity over one cell diagonal is `threshold`.  With min_cells > 1 or keep_largest the grid is then
+        `filtered`; with the defaults no component kernel runs."""
         resolution = int(resolution)
         lo, hi = _vec3(bbox_min), _vec3(bbox_max)
         sigma_thr = sigma_threshold(threshold, lo, hi, resolution)
         sigma = density_grid(model, params, lo, hi, resolution + 1, batch_size)
         bits, occupied = ops.occ_build(sigma.reshape(-1), resolution, sigma_thr, dilate)
-        return cls(bits=bits, resolution=resolution, bbox_min=lo, bbox_max=hi, sigma_thr=sigma_thr,
+        grid = cls(bits=bits, resolution=resolution, bbox_min=lo, bbox_max=hi, sigma_thr=sigma_thr,
                    occupied=occupied)
+        if min_cells != 1 or keep_largest is not None:
+            grid = grid.filtered(min_cells=min_cells, keep_largest=keep_largest, connectivity=connectivity)
+        return grid
 
     @classmethod
     def from_renderer(cls, renderer, resolution: int, threshold: float = 0.01, dilate: int = 1,
-                      batch_size: int = 1 << 18) -> "OccupancyGrid":
+                      batch_size: int = 1 << 18, min_cells: int = 1, keep_largest: Optional[int] = None,
+                      connectivity: int = 26) -> "OccupancyGrid":
         """The grid of a NeRFRenderer's fine model over its scene box."""
         return cls.from_model(renderer.fine, renderer.fine_params, renderer.bbox_min, renderer.bbox_max, resolution,
-                              threshold=threshold, dilate=dilate, batch_size=batch_size)
+                              threshold=threshold, dilate=dilate, batch_size=batch_size, min_cells=min_cells,
+                              keep_largest=keep_largest, connectivity=connectivity)
+
+    def cell_mask(self) -> torch.Tensor:
+        """The bitfield as uint8 [R, R, R], 1 = occupied (torch integer operations on the GPU)."""
+        shifts = torch.arange(32, dtype=torch.int32, device=self.bits.device)
+        cells = ((self.bits[:, None] >> shifts[None, :]) & 1).to(torch.uint8).reshape(-1)
+        r = self.resolution
+        return cells[:r ** 3].reshape(r, r, r).contiguous()
+
+    def filtered(self, min_cells: int = 1, keep_largest: Optional[int] = None,
+                 connectivity: int = 26) -> "OccupancyGrid":
+        """
+        The grid without its floaters (additive; learn_nerf/components.py): the connected components of the occupied
+        cells (the final, dilated bitfield the renderer walks) that have fewer than `min_cells` cells or, with
+        `keep_largest`, are not among the largest become unoccupied.  -> a new grid over the same box and resolution
+        with new bits and a new occupied count.  Run once per session: the bits are unpacked and repacked with torch.
+        """
+        from .components import keep_components
+
+        keep, _ = keep_components(self.cell_mask(), min_cells=min_cells, keep_largest=keep_largest,
+                                  connectivity=connectivity)
+        flat = keep.reshape(-1)
+        padded = torch.zeros(self.bits.numel() * 32, dtype=torch.int32, device=flat.device)
+        padded[:flat.numel()] = flat
+        shifts = torch.arange(32, dtype=torch.int32, device=flat.device)
+        # 32 distinct bits: the int32 sum is their union and cannot overflow (bit 31 is the only negative term)
+        bits = (padded.view(-1, 32) << shifts[None, :]).sum(dim=1, dtype=torch.int32)
+        return replace(self, bits=bits, occupied=int(flat.sum()))
 
     @property
     def occupied_fraction(self) -> float:

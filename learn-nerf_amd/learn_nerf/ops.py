@@ -122,6 +122,57 @@ def occ_clip_rays(rays, bbox_min: Sequence[float], bbox_max: Sequence[float], bi
     return lo, hi, out_mask
 
 
+def _cc_scratch(shape) -> int:
+    nx, ny, nz = (int(s) for s in shape)
+    if min(nx, ny, nz) < 1:
+        raise ValueError(f"connected components: every dimension must be at least 1, got {(nx, ny, nz)}")
+    nbytes = L.lib().lnrf_cc_scratch_bytes(nx, ny, nz)
+    if nbytes < 0:
+        raise ValueError(f"connected components: {(nx, ny, nz)} has more than 2^31 - 1 cells")
+    return nbytes
+
+
+def cc_local(mask: torch.Tensor, connectivity: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Per-tile labels (int32, the shape of the uint8 mask [nx, ny, nz]) and the scratch block that the merge rounds
+    of this labelling go on using."""
+    if mask.dim() != 3:
+        raise ValueError(f"expected a 3-d mask, got shape {tuple(mask.shape)}")
+    nx, ny, nz = mask.shape
+    nbytes = _cc_scratch(mask.shape)
+    labels = torch.empty(mask.shape, dtype=torch.int32, device=_dev(mask))
+    scratch = torch.empty(nbytes, dtype=torch.uint8, device=_dev(mask))
+    L.check(L.lib().lnrf_cc_local(L.ptr(mask, torch.uint8), nx, ny, nz, int(connectivity), L.ptr(labels, torch.int32),
+                                  L.ptr(scratch, torch.uint8), nbytes, L.stream()), "cc_local")
+    return labels, scratch
+
+
+def cc_merge_round(labels: torch.Tensor, scratch: torch.Tensor, changed: torch.Tensor, connectivity: int,
+                   round_index: int) -> None:
+    """One merge round in place on the labels and scratch of cc_local; `changed` (int32 [1]) is set by the round.
+    Raises at round_index = lnrf_cc_max_rounds()."""
+    nx, ny, nz = labels.shape
+    L.check(L.lib().lnrf_cc_merge_round(nx, ny, nz, int(connectivity), int(round_index), L.ptr(labels, torch.int32),
+                                        L.ptr(changed, torch.int32), L.ptr(scratch, torch.uint8), scratch.numel(),
+                                        L.stream()), "cc_merge_round")
+
+
+def cc_sizes(labels: torch.Tensor) -> torch.Tensor:
+    """int32 sizes, the shape of `labels`: the cell count of each component at its root index, 0 elsewhere."""
+    sizes = torch.empty_like(labels)
+    L.check(L.lib().lnrf_cc_sizes(L.ptr(labels, torch.int32), labels.numel(), L.ptr(sizes, torch.int32), L.stream()),
+            "cc_sizes")
+    return sizes
+
+
+def cc_keep(labels: torch.Tensor, sizes: torch.Tensor, min_cells: int, cut_size: int, cut_label: int) -> torch.Tensor:
+    """uint8 keep mask, the shape of `labels` (conventions: csrc/components.hip)."""
+    keep = torch.empty(labels.shape, dtype=torch.uint8, device=_dev(labels))
+    L.check(L.lib().lnrf_cc_keep(L.ptr(labels, torch.int32), L.ptr(sizes, torch.int32), labels.numel(),
+                                 int(min_cells), int(cut_size), int(cut_label), L.ptr(keep, torch.uint8), L.stream()),
+            "cc_keep")
+    return keep
+
+
 def stratified(t_min, t_max, count: int, u=None, seed: int = 0, stream_id: int = 0, ray_offset: int = 0):
     n = t_min.shape[0]
     ts = torch.empty((n, count), dtype=F32, device=_dev(t_min))

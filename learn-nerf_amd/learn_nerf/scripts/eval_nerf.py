@@ -23,7 +23,8 @@ from learn_nerf.scripts.render_nerf import RENDER_FLAGS, RenderSession, quantise
 from learn_nerf.scripts.train_nerf import add_model_args
 
 _SHARED = ("--batch_size", "--coarse_samples", "--fine_samples", "--model_path", "--occupancy_grid",
-           "--occupancy_threshold", "--occupancy_dilate")  # as in render_nerf.py: type, default and meaning
+           "--occupancy_threshold", "--occupancy_dilate", "--occupancy_min_component", "--occupancy_keep_largest",
+           "--occupancy_connectivity")  # as in render_nerf.py: type, default and meaning
 
 
 def build_parser() -> argparse.ArgumentParser:

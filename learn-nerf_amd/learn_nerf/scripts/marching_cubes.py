@@ -4,7 +4,9 @@ Mesh export with the command line of the reference's scripts/marching_cubes.py: 
 bounding box, marching cubes at --threshold (HIP, learn_nerf/mesh.py), OBJ or STL by the output's extension.
 Deliberate differences: a binary STL writer that works (the reference's cannot run), outward-wound faces, an error for
 an output extension other than .obj / .stl and for a grid where no occupancy exceeds the threshold, and one additive
-flag, --world_coords.
+flag, --world_coords.  Additive as well: --min_component / --keep_largest / --connectivity remove floaters, the connected
+components of {occupancy > threshold} that are small or not among the largest (learn_nerf/components.py), before the
+surface is extracted; without them nothing changes.
 """
 import argparse
 import sys
@@ -28,6 +30,12 @@ def build_parser() -> argparse.ArgumentParser:
     add_model_args(parser)
     parser.add_argument("--world_coords", action="store_true",
                         help="(additive) write scene coordinates instead of the reference's centred, x/z-swapped frame")
+    parser.add_argument("--min_component", type=int, default=1,
+                        help="(additive) drop connected components of the inside set with fewer grid points than this")
+    parser.add_argument("--keep_largest", type=int, default=None,
+                        help="(additive) keep only this many of the largest connected components")
+    parser.add_argument("--connectivity", type=int, default=26, choices=(6, 26),
+                        help="(additive) grid points are joined through faces (6) or faces, edges and corners (26)")
     parser.add_argument("metadata_json", type=str)
     parser.add_argument("output_obj", type=str, help="output mesh, .obj or .stl")
     return parser
@@ -41,6 +49,8 @@ def main(argv=None):
         parser.error(f"output_obj must end in .obj or .stl: {args.output_obj!r}")
     if args.resolution < 2 or args.batch_size < 1:
         parser.error("--resolution must be at least 2 and --batch_size positive")
+    if args.min_component < 1 or (args.keep_largest is not None and args.keep_largest < 1):
+        parser.error("--min_component and --keep_largest must be at least 1")
 
     print("loading metadata...")
     metadata = ModelMetadata.from_json(args.metadata_json)
@@ -52,7 +62,14 @@ def main(argv=None):
 
     print("computing densities...")
     box = (metadata.bbox_min, metadata.bbox_max, args.resolution)
-    verts, faces, largest = extract_mesh(fine, params, *box, args.batch_size, args.threshold)
+    found = {}
+    verts, faces, largest = extract_mesh(fine, params, *box, args.batch_size, args.threshold,
+                                         min_component=args.min_component, keep_largest=args.keep_largest,
+                                         connectivity=args.connectivity, info=found)
+    if found:  # a filter is active
+        print(f"components: kept {found['kept']} of {found['components']}, removed {found['removed']} points")
+        if found["components"] and not found["kept"]:
+            sys.exit(f"no surface: the filter removed all {found['components']} components")
     if faces.shape[0] == 0:
         sys.exit(f"no surface: no occupancy exceeds the threshold {args.threshold} (largest occupancy {largest:.6g})")
     verts, faces = verts.cpu().numpy(), faces.cpu().numpy()

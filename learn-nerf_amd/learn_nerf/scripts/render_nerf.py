@@ -29,6 +29,10 @@ RENDER_FLAGS = (
     ("--occupancy_grid", int, 0, "cells per axis of the occupancy grid; 0 = off (render every sample)"),
     ("--occupancy_threshold", float, 0.01, "opacity of one cell diagonal below which a cell counts as empty"),
     ("--occupancy_dilate", int, 1, "cells by which the occupied set is grown"),
+    # floater removal on the grid (learn_nerf/components.py); the defaults leave the grid as it is built
+    ("--occupancy_min_component", int, 1, "drop connected components of occupied cells with fewer cells than this"),
+    ("--occupancy_keep_largest", int, None, "keep only this many of the largest components of occupied cells"),
+    ("--occupancy_connectivity", int, 26, "cells are joined through faces (6) or faces, edges and corners (26)"),
 )
 
 
@@ -63,7 +67,10 @@ class RenderSession:
         resolution = getattr(args, "occupancy_grid", 0)
         if resolution > 0:
             grid = OccupancyGrid.from_renderer(self.renderer, resolution, threshold=args.occupancy_threshold,
-                                               dilate=args.occupancy_dilate)
+                                               dilate=args.occupancy_dilate,
+                                               min_cells=getattr(args, "occupancy_min_component", 1),
+                                               keep_largest=getattr(args, "occupancy_keep_largest", None),
+                                               connectivity=getattr(args, "occupancy_connectivity", 26))
             print(f"occupancy grid {resolution}^3: {grid.occupied} of {resolution ** 3} cells occupied "
                   f"({100.0 * grid.occupied_fraction:.2f}%)")
             self.renderer.occupancy = grid
