@@ -134,6 +134,17 @@ int lnrf_composite_bwd_det(const float* ts, const float* t_min, const float* t_m
                            float* g_density, float* g_rgb, float* g_aux, float* g_background, void* scratch,
                            int64_t scratch_bytes, lnrf_stream_t stream);
 
+/* Distortion loss of mip-NeRF 360 (Barron et al. 2022, eq. 15) on the compositing weights of each ray, and its
+ * gradient to the densities.  With the bins, a_i and A_i of lnrf_termination_probs, w_i = probs[n, i] for i < T (the
+ * background's share takes no part), r = t_max - t_min, m_i = ((start_i + end_i) / 2 - t_min) / r, d_i = delta_i / r:
+ *   L_n = sum_i sum_j w_i w_j |m_i - m_j| + (1/3) sum_i w_i^2 d_i
+ * loss[N] = L_n is written (may be NULL); g_density[N,T] += grad_scale * dL_n/dsigma (may be NULL; not both).
+ * A ray with mask == 0, r <= 0 or a non-finite r has loss 0 and its g_density row is left untouched.  No gradient
+ * flows to ts, t_min or t_max.  One launch, no scratch; each ray's result depends on that ray alone (bit-reproducible). */
+int lnrf_distortion(const float* ts, const float* t_min, const float* t_max, const uint8_t* mask,
+                    const float* density, int64_t n_rays, int32_t t, float grad_scale, float* loss,
+                    float* g_density, lnrf_stream_t stream);
+
 /* ----------------------------------------------------------- generic dense ---- */
 
 /* sinusoidal_emb (model.py:65-77): out[m, col_off + c*2F + {f | F+f}] = sin|cos(2^f x[m,c]).

@@ -346,6 +346,127 @@ __global__ __launch_bounds__(256) void composite_bg_fold_kernel(const float* __r
   if (threadIdx.x < 3) atomicAdd(g_background + threadIdx.x, red[0][threadIdx.x]);
 }
 
+// ---------------------------------------------------------------------------------------
+// Distortion loss (mip-NeRF 360, Barron et al. 2022, eq. 15) of a ray's compositing weights, and its gradient.
+// For ray n with mask[n] != 0 and T >= 1 ascending samples, bins as in quad_chunk (start_0 = t_min, end_{T-1} = t_max,
+// midpoints of neighbouring samples otherwise):
+//   delta_i = end_i - start_i,  a_i = sigma_i delta_i,  A_i = sum_{j<=i} a_j,
+//   w_i = exp(-A_{i-1}) (1 - exp(-a_i))       the first T termination probabilities; the background's share
+//                                             exp(-A_{T-1}) takes no part,
+//   r = t_max - t_min,  m_i = ((start_i + end_i) / 2 - t_min) / r,  d_i = delta_i / r      (scale-free),
+//   L_n = sum_i sum_j w_i w_j |m_i - m_j| + (1/3) sum_i w_i^2 d_i.
+// A ray with mask == 0, with r <= 0 or with a non-finite r has L_n = 0 and no gradient.
+// m is ascending, so with the exclusive prefixes W_<i = sum_{j<i} w_j, M_<i = sum_{j<i} w_j m_j (and suffixes W_>i, M_>i):
+//   L_n = 2 sum_i w_i (m_i W_<i - M_<i) + (1/3) sum_i w_i^2 d_i
+//   G_i = dL_n/dw_i = 2 (m_i W_<i - M_<i + M_>i - m_i W_>i) + (2/3) w_i d_i
+//   dL_n/dsigma_k = delta_k (G_k exp(-A_k) - sum_{i>k} G_i w_i).
+// No gradient flows to ts, t_min or t_max (render.py:76).
+//
+// One wave per ray, chunks of 64 samples, every running sum carried across chunks.  Sweep 1 forms the loss and, as the
+// last inclusive values of its two scans, the totals W_T and M_T; sweep 2 forms Gamma = sum_i G_i w_i; sweep 3 writes
+// delta_k (G_k exp(-A_k) - (Gamma - inclusive scan of G w)), the total-minus-prefix device of composite_bwd_kernel.
+// Sweeps 2 and 3 run only when a gradient is asked for; the loss has the same bits either way.  A ray's row is a few KB
+// and stays in cache between the sweeps.  No LDS, no atomics: each ray's result depends on that ray alone.
+struct Dist {
+  float w, m, d, delta;   // weight, normalised bin centre and width, bin width
+  float incl;             // A_i
+  float w_ex, m_ex;       // W_<i, M_<i
+  float w_in, m_in;       // W_<=i, M_<=i
+};
+
+struct DistCarry {
+  float a, w, m;          // A, W, M up to the end of the previous chunk
+};
+
+__device__ __forceinline__ Dist dist_chunk(const float* __restrict__ ts_row, const float* __restrict__ dens_row,
+                                           int T, int i, int lane, float tmin, float tmax, float r, DistCarry& c) {
+  const Quad q = quad_chunk(ts_row, dens_row, T, i, lane, tmin, tmax, c.a);
+  const bool valid = i < T;
+  const int ic = valid ? i : T - 1;
+  const float t_p = ic > 0 ? ts_row[ic - 1] : 0.0f;
+  const float start = ic == 0 ? tmin : (q.t + t_p) / 2.0f;
+  Dist s;
+  s.delta = q.end - start;
+  s.w = valid ? expf(-q.prev) * (1.0f - expf(-q.a)) : 0.0f;
+  s.m = ((start + q.end) / 2.0f - tmin) / r;
+  s.d = s.delta / r;
+  s.incl = q.incl;
+  s.w_in = wave_incl_scan(s.w, lane) + c.w;
+  s.m_in = wave_incl_scan(s.w * s.m, lane) + c.m;
+  const float w_up = __shfl_up(s.w_in, 1, 64), m_up = __shfl_up(s.m_in, 1, 64);
+  s.w_ex = lane == 0 ? c.w : w_up;
+  s.m_ex = lane == 0 ? c.m : m_up;
+  c.a = __shfl(q.incl, 63, 64);
+  c.w = __shfl(s.w_in, 63, 64);
+  c.m = __shfl(s.m_in, 63, 64);
+  return s;
+}
+
+__device__ __forceinline__ float dist_g(const Dist& s, float w_tot, float m_tot) {
+  return 2.0f * (s.m * s.w_ex - s.m_ex + (m_tot - s.m_in) - s.m * (w_tot - s.w_in)) + (2.0f / 3.0f) * s.w * s.d;
+}
+
+// g + grad_scale * v with the product rounded on its own (contraction off: hipcc would fuse the two into one fma), so a
+// call into a filled row adds exactly the fp32 value that a call into a zeroed row stores
+__device__ __forceinline__ float dist_accumulate(float g, float grad_scale, float v) {
+#pragma clang fp contract(off)
+  const float x = grad_scale * v;
+  return g + x;
+}
+
+__global__ __launch_bounds__(256) void distortion_kernel(const float* __restrict__ ts, const float* __restrict__ t_min,
+                                                         const float* __restrict__ t_max,
+                                                         const uint8_t* __restrict__ mask,
+                                                         const float* __restrict__ density, int64_t n_rays, int T,
+                                                         float grad_scale, float* __restrict__ loss,
+                                                         float* __restrict__ g_density) {
+  const int lane = threadIdx.x & 63;
+  const int64_t n = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+  if (n >= n_rays) return;
+  const float tmin = t_min[n], tmax = t_max[n];
+  const float r = tmax - tmin;
+  if (mask[n] == 0 || !(r > 0.0f) || !(r <= 3.402823466e38f)) {
+    if (loss && lane == 0) loss[n] = 0.0f;
+    return;
+  }
+  const float* ts_row = ts + n * T;
+  const float* de_row = density + n * T;
+  // sweep 1: the loss and the totals
+  DistCarry c = {0.0f, 0.0f, 0.0f};
+  float l_part = 0.0f;
+  for (int base = 0; base < T; base += 64) {
+    const Dist s = dist_chunk(ts_row, de_row, T, base + lane, lane, tmin, tmax, r, c);
+    l_part += 2.0f * s.w * (s.m * s.w_ex - s.m_ex) + (1.0f / 3.0f) * s.w * s.w * s.d;
+  }
+  const float w_tot = c.w, m_tot = c.m;
+  const float l = wave_sum(l_part);
+  if (loss && lane == 0) loss[n] = l;
+  if (!g_density) return;
+  // sweep 2: Gamma = sum_i G_i w_i
+  c = {0.0f, 0.0f, 0.0f};
+  float gw_part = 0.0f;
+  for (int base = 0; base < T; base += 64) {
+    const Dist s = dist_chunk(ts_row, de_row, T, base + lane, lane, tmin, tmax, r, c);
+    gw_part += dist_g(s, w_tot, m_tot) * s.w;
+  }
+  const float gamma = wave_sum(gw_part);
+  // sweep 3: the gradient
+  c = {0.0f, 0.0f, 0.0f};
+  float gw_carry = 0.0f;
+  for (int base = 0; base < T; base += 64) {
+    const int i = base + lane;
+    const Dist s = dist_chunk(ts_row, de_row, T, i, lane, tmin, tmax, r, c);
+    const float gk = dist_g(s, w_tot, m_tot);
+    const float gw_incl = wave_incl_scan(gk * s.w, lane) + gw_carry;
+    if (i < T) {
+      const float v = s.delta * (gk * expf(-s.incl) - (gamma - gw_incl));
+      const int64_t e = n * T + i;
+      g_density[e] = dist_accumulate(g_density[e], grad_scale, v);
+    }
+    gw_carry = __shfl(gw_incl, 63, 64);
+  }
+}
+
 // fine_sampling (render.py:211-257). One wave per ray; LDS per wave: xs[tc+1], ys[tc+1],
 // comb[tc+tf].  The final jnp.sort is exact for any input (merge ranks when both lists are in order, rank count otherwise).
 __global__ void fine_sample_kernel(const float* __restrict__ ts_c, const float* __restrict__ t_min,
@@ -631,6 +752,20 @@ extern "C" int lnrf_composite_bwd_det(const float* ts, const float* t_min, const
                        (int)((n_rays + wpb - 1) / wpb), g_background);
     LNRF_LAUNCH_CHECK();
   }
+  return LNRF_OK;
+}
+
+extern "C" int lnrf_distortion(const float* ts, const float* t_min, const float* t_max, const uint8_t* mask,
+                               const float* density, int64_t n_rays, int32_t t, float grad_scale, float* loss,
+                               float* g_density, lnrf_stream_t stream) {
+  LNRF_CHECK_ARG(n_rays >= 0 && t >= 1, "bad sizes");
+  LNRF_CHECK_ARG(loss || g_density, "both outputs are NULL");
+  if (n_rays == 0) return LNRF_OK;
+  LNRF_CHECK_ARG(ts && t_min && t_max && mask && density, "null pointer");
+  const int wpb = 4;
+  hipLaunchKernelGGL(distortion_kernel, dim3((unsigned)((n_rays + wpb - 1) / wpb)), dim3(wpb * 64), 0,
+                     as_stream(stream), ts, t_min, t_max, mask, density, n_rays, (int)t, grad_scale, loss, g_density);
+  LNRF_LAUNCH_CHECK();
   return LNRF_OK;
 }
 

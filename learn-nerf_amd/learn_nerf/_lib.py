@@ -69,6 +69,7 @@ PROTOTYPES = {
     "lnrf_composite_bwd_scratch_bytes": (c_int64, [c_int64]),
     "lnrf_composite_bwd_det": (c_int32, [_P, _P, _P, _P, _P, _P, _P, c_int32, _P, c_int64, c_int32, _P, _P, _P,
                                          c_int64, c_float, _F3, _P, _P, _P, _P, _P, c_int64, _P]),
+    "lnrf_distortion": (c_int32, [_P, _P, _P, _P, _P, c_int64, c_int32, c_float, _P, _P, _P]),
     "lnrf_sinusoidal_emb": (c_int32, [_P, c_int64, c_int64, c_int32, c_int32, _P, c_int64, c_int64, _P]),
     "lnrf_dense_fwd": (c_int32, [_P, c_int64, _P, _P, c_int32, _P, c_int64, c_int64, c_int32, c_int32, _P]),
     "lnrf_act_bwd": (c_int32, [_P, c_int64, _P, c_int64, c_int32, c_int64, c_int32, _P]),

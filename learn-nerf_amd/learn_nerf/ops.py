@@ -274,6 +274,17 @@ def composite_bwd(ts, t_min, t_max, mask, density, rgb, background, g_background
     return g_density, g_rgb, g_aux
 
 
+def distortion(ts, t_min, t_max, mask, density, g_density=None, grad_scale: float = 0.0, want_loss: bool = True):
+    """Distortion loss per ray (lnrf_distortion) -> loss[N] | None; g_density[N,T] += grad_scale * dL_n/dsigma if given."""
+    n, t = ts.shape
+    assert want_loss or g_density is not None
+    assert density.shape == (n, t) and (g_density is None or g_density.shape == (n, t))
+    loss = torch.empty(n, dtype=F32, device=_dev(ts)) if want_loss else None
+    L.check(L.lib().lnrf_distortion(L.ptr(ts), L.ptr(t_min), L.ptr(t_max), L.ptr(mask, torch.uint8), L.ptr(density),
+                                    n, t, float(grad_scale), L.ptr(loss), L.ptr(g_density), L.stream()), "distortion")
+    return loss
+
+
 # ---------------------------------------------------------------- generic dense (exact fp32)
 
 _DENSE_PRECISIONS = {"fp32": 0, "bf16": 1}  # LNRF_DENSE_FP32 / LNRF_DENSE_BF16

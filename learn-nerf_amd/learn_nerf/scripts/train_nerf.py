@@ -1,8 +1,8 @@
 """
 Training CLI with the command line of the reference's scripts/train_nerf.py (same flag names, defaults,
 positional `data_dir`, `step {i}: k=v ...` log lines, resume-if-checkpoint-exists, periodic save), driving
-the HIP train step.  Extra, additive flags: --precision, --max_steps, --table_log2.  Under torchrun every global batch is
-sharded over the ranks and gradients are all-reduced over RCCL.
+the HIP train step.  Extra, additive flags: --precision, --max_steps, --table_log2, --distortion_weight.  Under torchrun
+every global batch is sharded over the ranks and gradients are all-reduced over RCCL.
 """
 import argparse
 import os
@@ -28,6 +28,7 @@ TRAIN_FLAGS = (
     ("--fine_samples", int, 128, "samples per fine ray (not including coarse samples)"),
     ("--density_penalty", float, None, "penalty coefficient for density at random points"),
     ("--density_penalty_batch_size", int, 128, "batch size for computing density penalty"),
+    ("--distortion_weight", float, None, "(additive) distortion loss weight of both passes; 0 logs it only"),
     ("--save_interval", int, 1000, None),
     ("--save_path", str, "nerf.pkl", None),
     ("--test_data_dir", str, None, None),
@@ -114,7 +115,8 @@ def main():
     coarse, fine, extra = create_model(args, data.metadata)
     loop = TrainLoop(coarse, fine, init_rng=init_key.seed, lr=args.lr, coarse_ts=args.coarse_samples,
                      fine_ts=args.fine_samples, density_penalty=args.density_penalty,
-                     density_penalty_batch_size=args.density_penalty_batch_size, **extra)
+                     density_penalty_batch_size=args.density_penalty_batch_size,
+                     distortion_weight=args.distortion_weight, **extra)
     if os.path.exists(args.save_path):
         say(f"loading from checkpoint: {args.save_path}")
         loop.load(args.save_path)

@@ -65,6 +65,7 @@ class TrainLoop:
         density_penalty: Optional[float] = None,
         density_penalty_batch_size: int = 128,
         device=None,
+        distortion_weight: Optional[float] = None,
     ):
         self.coarse = coarse
         self.fine = fine
@@ -76,6 +77,9 @@ class TrainLoop:
         self.loss_weights = loss_weights if loss_weights is not None else default_loss_weights()
         self.density_penalty = density_penalty
         self.density_penalty_batch_size = density_penalty_batch_size
+        # weight of the mean per-ray distortion loss (mip-NeRF 360 eq. 15; csrc/rays.hip distortion_kernel) of the coarse
+        # and of the fine pass.  None: the kernel never runs; 0.0: the two means are logged and nothing else changes
+        self.distortion_weight = distortion_weight
         self.device = device if device is not None else default_device()
 
         # train.py:47-58: split the init key, init both models, background = all black (-1,-1,-1)
@@ -193,18 +197,24 @@ class TrainLoop:
         out_scale = 2.0 * inv  # d mean((out-t)^2) / d out
         gc, gf, gbg = self._slices(grad_flat) if want_grad else (None, None, None)
 
-        def output_grads(ts, dens, rgb, out, names, auxs):
+        dist_w = self.distortion_weight
+        dist_rays = {}  # pass -> per-ray distortion loss [N]
+
+        def output_grads(prefix, ts, dens, rgb, out, names, auxs):
             gw = [self.loss_weights[k] / n for k in names]
             gd, grgb, gaux = ops.composite_bwd(ts, t_min, t_max, mask, dens, rgb, bg, gbg, outputs=out,
                                                targets=targets, out_scale=out_scale, aux=auxs, g_aux_w=gw)
+            if dist_w is not None:  # on the stream composite_bwd ran on: gd += (dist_w / n) dL_n/dsigma
+                dist_rays[prefix] = ops.distortion(ts, t_min, t_max, mask, dens, g_density=gd if dist_w != 0.0 else None,
+                                                   grad_scale=dist_w / n)
             g_aux = {k: gaux[..., i] for i, k in enumerate(names)} if names else None
             return gd, grgb, g_aux
 
-        def backward_of(ts, dens, rgb, out, model, ctx, gslice, names, auxs):
-            gd, grgb, g_aux = output_grads(ts, dens, rgb, out, names, auxs)
+        def backward_of(prefix, ts, dens, rgb, out, model, ctx, gslice, names, auxs):
+            gd, grgb, g_aux = output_grads(prefix, ts, dens, rgb, out, names, auxs)
             model.backward(ctx, gd, grgb, g_aux, gslice)
 
-        coarse_args = (ts_c, dens_c, rgb_c, out_c, self.coarse, ctx_c, gc, names_c, auxs_c)
+        coarse_args = ("coarse", ts_c, dens_c, rgb_c, out_c, self.coarse, ctx_c, gc, names_c, auxs_c)
         coarse_done = None
         if want_grad and self.overlap_backward:
             if self._side_stream is None:
@@ -235,8 +245,8 @@ class TrainLoop:
             # both models are fused NeRFModels on the layer-stationary backward: one persistent launch for the two
             from .model import backward_ls_pair
 
-            gd_c, grgb_c, _ = output_grads(ts_c, dens_c, rgb_c, out_c, names_c, auxs_c)
-            gd_f, grgb_f, _ = output_grads(ts_f, dens_f, rgb_f, out_f, names_f, auxs_f)
+            gd_c, grgb_c, _ = output_grads("coarse", ts_c, dens_c, rgb_c, out_c, names_c, auxs_c)
+            gd_f, grgb_f, _ = output_grads("fine", ts_f, dens_f, rgb_f, out_f, names_f, auxs_f)
             backward_ls_pair(ctx_c, gd_c, grgb_c, gc, ctx_f, gd_f, grgb_f, gf)
         elif want_grad:
             if coarse_done is None:
@@ -244,9 +254,19 @@ class TrainLoop:
                 if self.density_penalty is None:
                     # the coarse model's gradient is final: its all-reduce runs under the fine backward (data parallel)
                     self._early_reduce = (self.n_coarse, parallel.begin_reduce_(gc))
-            backward_of(ts_f, dens_f, rgb_f, out_f, self.fine, ctx_f, gf, names_f, auxs_f)
+            backward_of("fine", ts_f, dens_f, rgb_f, out_f, self.fine, ctx_f, gf, names_f, auxs_f)
             if coarse_done is not None:
                 torch.cuda.current_stream(self.device).wait_event(coarse_done)  # join before anything reads the gradient
+
+        if dist_w is not None:
+            if not want_grad:
+                dist_rays["coarse"] = ops.distortion(ts_c, t_min, t_max, mask, dens_c)
+                dist_rays["fine"] = ops.distortion(ts_f, t_min, t_max, mask, dens_f)
+            elif coarse_done is not None:
+                # written on the side stream, read here after the join: keep its memory from being reused over there
+                dist_rays["coarse"].record_stream(torch.cuda.current_stream(self.device))
+            for prefix in ("coarse", "fine"):
+                loss_dict[f"{prefix}_distortion"] = dist_rays[prefix].mean()
 
         if self.density_penalty is not None:  # train.py:153-163
             gsl = self._slices(grad_flat) if want_grad else (None, None, None)
@@ -317,6 +337,8 @@ class TrainLoop:
                         total = total + self.loss_weights[name] * v
                     elif name == "density" and self.density_penalty is not None:
                         total = total + self.density_penalty * v
+                    elif name == "distortion" and self.distortion_weight is not None:
+                        total = total + self.distortion_weight * v
         return total, loss_dict
 
     def _flat_from_params(self, params) -> torch.Tensor:
