@@ -758,6 +758,45 @@ int lnrf_cc_sizes(const int32_t* labels, int64_t n, int32_t* sizes, lnrf_stream_
 int lnrf_cc_keep(const int32_t* labels, const int32_t* sizes, int64_t n, int32_t min_cells, int32_t cut_size,
                  int32_t cut_label, uint8_t* keep, lnrf_stream_t stream);
 
+/* ------------------------------------------------------------- TSDF fusion ---- */
+
+/* Truncated-signed-distance fusion of RGB-D views into a grid of nx x ny x nz points (additive; csrc/tsdf.hip, and
+ * csrc/tsdf_geom.h for the arithmetic, operation by operation; learn_nerf/tsdf.py drives it).  Grid point (i, j, k) is
+ * at (xs[i], ys[j], zs[k]) (device arrays) and has linear index (i*ny + j)*nz + k.  Every dimension >= 1 and
+ * (nx+2)(ny+2)(nz+2) <= INT32_MAX, else LNRF_ERR_SHAPE (checked before any pointer is looked at).  No entry point
+ * allocates, copies or synchronises.
+ * State, caller-owned and zeroed before the first view: sum_t f32 [N], n_obs i32 [N], behind u8 [N], rgb_sum i32 [N, 3],
+ * n_col i32 [N]. */
+typedef struct lnrf_tsdf_view {
+  float origin[3];
+  float inv[9];    /* rows of M^-1, M = [tan(x_fov/2) x_axis | tan(y_fov/2) y_axis | camera_direction] (columns) */
+  float zaxis[3];  /* camera_direction */
+  int32_t width, height; /* each >= 2 */
+  int32_t pad_;
+  int64_t depth_offset; /* element offset of this view's uint16 [height, width] z-depth in `depth` */
+  int64_t color_offset; /* element offset of this view's uint8 [height, width, 3] RGB image in `color` */
+} lnrf_tsdf_view;
+
+/* Adds views[0 .. n_views) (a device array), in order, to the state.  depth / color: the packed device buffers that
+ * the descriptors' offsets index; a view's images must lie inside them (not checked: the descriptors are on the
+ * device).  z-depth = (float)d16 / 65535 * max_depth, 0xFFFF = nothing hit; with carve != 0 such a pixel counts as
+ * free space (sum_t += 1).  trunc, max_depth > 0 and finite (LNRF_ERR_ARG).  One lane owns a voxel: no atomics, and
+ * the same bits however the views are split over calls.  n_views = 0 launches nothing. */
+int lnrf_tsdf_integrate(const float* xs, const float* ys, const float* zs, int64_t nx, int64_t ny, int64_t nz,
+                        const lnrf_tsdf_view* views, int64_t n_views, const uint16_t* depth, const uint8_t* color,
+                        float trunc, float max_depth, int32_t carve, float* sum_t, int32_t* n_obs, uint8_t* behind,
+                        int32_t* rgb_sum, int32_t* n_col, lnrf_stream_t stream);
+/* out fp32 [nx+2, ny+2, nz+2], ready for lnrf_mc_* at level 0 (inside = out > 0): -1 on the padding layer and -F at
+ * the grid points, F = sum_t / (float)n_obs where n_obs > 0, else -1 when behind and unseen_inside != 0, else +1. */
+int lnrf_tsdf_volume(const float* sum_t, const int32_t* n_obs, const uint8_t* behind, int64_t nx, int64_t ny,
+                     int64_t nz, int32_t unseen_inside, float* out, lnrf_stream_t stream);
+/* rgb_out fp32 [n, 3] in [0, 1] for the vertices verts [n, 3] of lnrf_mc_emit on that volume (padded index space):
+ * the mean colours rgb_sum / n_col / 255 of the two grid points of the vertex's edge, interpolated as the vertex is;
+ * the one that has a colour when the other has none; 0.5 grey when neither has.  n_missing: one device int32, cleared
+ * first, = the number of grey vertices (integer atomics: exact).  0 <= n <= INT32_MAX, else LNRF_ERR_SHAPE. */
+int lnrf_tsdf_vertex_colors(const float* verts, int64_t n, int64_t nx, int64_t ny, int64_t nz, const int32_t* rgb_sum,
+                            const int32_t* n_col, float* rgb_out, int32_t* n_missing, lnrf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -186,6 +186,10 @@ PROTOTYPES = {
     "lnrf_cc_merge_round": (c_int32, [c_int64, c_int64, c_int64, c_int32, c_int32, _P, _P, _P, c_int64, _P]),
     "lnrf_cc_sizes": (c_int32, [_P, c_int64, _P, _P]),
     "lnrf_cc_keep": (c_int32, [_P, _P, c_int64, c_int32, c_int32, c_int32, _P, _P]),
+    "lnrf_tsdf_integrate": (c_int32, [_P, _P, _P, c_int64, c_int64, c_int64, _P, c_int64, _P, _P, c_float, c_float,
+                                      c_int32, _P, _P, _P, _P, _P, _P]),
+    "lnrf_tsdf_volume": (c_int32, [_P, _P, _P, c_int64, c_int64, c_int64, c_int32, _P, _P]),
+    "lnrf_tsdf_vertex_colors": (c_int32, [_P, c_int64, c_int64, c_int64, c_int64, _P, _P, _P, _P, _P]),
 }
 
 _lib = None
