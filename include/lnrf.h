@@ -643,6 +643,43 @@ int lnrf_rt_closest(const lnrf_rt_bvh* bvh, const float* sorted_tris, const int3
 int lnrf_rt_occluded(const lnrf_rt_bvh* bvh, const float* sorted_tris, const float* nodes, const float* rays,
                      const float* window, int64_t m, uint8_t* out, lnrf_stream_t stream);
 
+/* ---------------------------------------------------------- mesh comparison ---- */
+
+/* Point-to-mesh queries and surface sampling behind learn_nerf/mesh_metrics.py and scripts/eval_mesh.py, over the tree
+ * above (bvh, sorted_tris, order, nodes exactly as lnrf_rt_morton / lnrf_rt_fit leave them).  The pinned fp32
+ * point-triangle distance, the tie rule, the margin of the box test with its derivation and the domain: the header
+ * comment of csrc/raycast.hip, section "Nearest triangle"; areas, sampling and the statistics: csrc/mesh_metrics.hip.
+ * No entry point allocates, copies, synchronises or uses atomics; every output element is written. */
+
+/* out_d2 / out_id [m]: the pinned squared distance from each point of pts [m, 3] to the nearest triangle and that
+ * triangle's original index order[j], the lowest index among equal d2.  out_point (nullable) [m, 3]: the closest point
+ * of that triangle.  Results do not depend on leaf_size. */
+int lnrf_mesh_nearest(const lnrf_rt_bvh* bvh, const float* sorted_tris, const int32_t* order, const float* nodes,
+                      const float* pts, int64_t m, float* out_d2, int32_t* out_id, float* out_point,
+                      lnrf_stream_t stream);
+/* areas [n] fp32 of tris [n, 3, 3]: 0.5 * sqrt(|e1 x e2|^2), every operation rounded once, sqrt correctly rounded. */
+int lnrf_mesh_tri_areas(const float* tris, int64_t n, float* areas, lnrf_stream_t stream);
+/* m stratified samples in proportion to area.  cdf [n] (device float64): non-decreasing running sum of the areas of
+ * tris [n, 3, 3] in their order, the total last (> 0, finite; the caller checks).  Sample i draws u0, u1, u2 = elements
+ * 3i, 3i + 1, 3i + 2 of Philox stream stream_id under seed (csrc/philox.h); x = ((i + u0) / m) * total in fp64; its
+ * triangle is the first j with cdf[j] > x, or, when there is none, the first j with cdf[j] >= total (the last triangle
+ * of positive area), so a zero-area triangle is never chosen; (u1, u2) is folded to (1 - u1, 1 - u2) if u1 + u2 > 1 and
+ * the point is (v0 + u1 * e1) + u2 * e2 in fp32, one rounding per operation.  pts [m, 3]; ids [m]: order[j], or j when
+ * order is NULL.  1 <= n <= 2^28, 0 <= m < 2^40. */
+int lnrf_mesh_sample_surface(const float* tris, const int32_t* order, const double* cdf, int64_t n, int64_t m,
+                             uint64_t seed, uint32_t stream_id, float* pts, int32_t* ids, lnrf_stream_t stream);
+/* Statistics of m squared distances d2 [m] fp32 (finite, >= 0) in fp64 and in the fixed order of the dataset
+ * diagnostics below (min(ceil(m / 256), 1024) workgroups of 256 leave their partials in `scratch`, 8-byte aligned, and
+ * a second launch of one workgroup folds them; every partial that is read is written first).  acc: device double
+ * [4 + n_thresholds]: acc[0] += sum sqrt(double(d2)), acc[1] += sum double(d2), acc[2] += sum |double(cosine)| (cosine
+ * [m] fp32, nullable: acc[2] is then left alone), acc[3] = max(acc[3], max d2), acc[4 + k] += the number of elements
+ * with sqrt(double(d2)) <= thresholds[k] (as a double: exact below 2^53).  thresholds: (host) n_thresholds <= 8
+ * doubles.  Successive calls on one stream may share acc.  m == 0 returns LNRF_OK and touches nothing.
+ * scratch: lnrf_dist_stats_scratch_bytes(m) bytes (-1 for m < 0). */
+int64_t lnrf_dist_stats_scratch_bytes(int64_t m);
+int lnrf_dist_stats_f64(const float* d2, const float* cosine, int64_t m, const double* thresholds,
+                        int32_t n_thresholds, double* acc, void* scratch, int64_t scratch_bytes, lnrf_stream_t stream);
+
 /* ------------------------------------------------------ dataset diagnostics ---- */
 
 /* Whole-view reductions behind scripts/cv_nerf.py and scripts/check_bbox.py (csrc/view_stats.hip), with a FIXED order

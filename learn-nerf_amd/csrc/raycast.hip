@@ -46,6 +46,44 @@
 // A direction component of exactly 0 has an infinite reciprocal: a plane distance times it is -inf or +inf (the axis
 // then constrains nothing, or everything when the origin is outside the slab), and 0 * inf = NaN, the origin exactly
 // on a plane, drops that axis' constraint.  A flat box (an axis-aligned triangle) is a slab of width 2 mu.
+//
+// Nearest triangle (lnrf_mesh_nearest; learn_nerf/mesh_metrics.py, tests/mesh_metrics_reference.py restates it bit for
+// bit).  For a point p and a triangle a, b, c = v0, v1, v2, in fp32 with every operation rounded once (contraction
+// off), dot and cross as above:
+//   e1 = b - a, e2 = c - a, e3 = c - b, w = p - a, z = p - b;
+//   seg(w, d): dd = d . d, wd = w . d, t = dd > 0 ? wd / dd (IEEE) : 0, then t = t > 0 ? t : 0, t = t < 1 ? t : 1,
+//              r = w - t * d per component, value r . r;
+//   d2 starts at +inf and takes, in this order and only where STRICTLY smaller, seg(w, e1) [edge a-b], seg(z, e3)
+//   [b-c], seg(w, e2) [a-c], and the face: n = e1 x e2, nn = n . n; if nn > 0: u = ((w x e2) . n) / nn,
+//   v = ((e1 x w) . n) / nn, and if u >= 0 && v >= 0 && u + v <= 1: r = (w - u * e1) - v * e2, value r . r.
+//   Closest point (optional output): a + t * e1, b + t * e3, a + t * e2 or (a + u * e1) + v * e2 of the winner.
+// A zero-length edge takes t = 0 and a zero normal skips the face, so a triangle collapsed to a segment or a point gives
+// the distance to that segment or point and nothing divides 0 by 0: no NaN for any finite triangle of the domain.
+// Every candidate is the distance to a point OF the triangle (t in [0, 1]; u, v >= 0, u + v <= 1), and every vector is
+// relative (p - a, never an absolute position), which is what the margin below rests on.  nearest: the smallest d2
+// and the original index of its triangle; among equal d2 the lowest original index.
+// Box test: g.x = max(max((lo.x - p.x) - mu, (p.x - hi.x) - mu), 0), likewise y and z, D2 = (g.x^2 + g.y^2) + g.z^2;
+// a node is skipped iff D2 > best d2 so far — strictly, so an equal d2 with a lower index is still reached; an empty
+// node (lo > hi) is skipped; the box (-inf, +inf) of the slivers gives -inf - mu = -inf, g = 0, D2 = 0, never NaN: they
+// are always tested.  mu = 2^-11 * rho with the rho of the ray code, rho = |p - c|_1 + 3 * radius >= S + E for S the
+// distance from p to any vertex and E any edge.
+// Claim: a triangle i whose pinned d2 is <= the running best is never inside a skipped node.  With eps = 2^-24:
+// (1) The pinned value is not far BELOW the distance to the triangle's box.  The winning candidate is |r|^2 for
+// r = w - t d (or (w - u e1) - v e2).  In exact arithmetic on the rounded t (u, v) that is p - q for a point q of the
+// triangle (up to eps E, from fl(u + v) <= 1), and q lies in the box of every node that holds i, so per axis
+// |p - q| >= the exact gap g* of that box.  The roundings: w and d are off by eps |w| and eps |d|, the product t d by
+// another eps |d|, the difference by eps |r| — at most eps (|w| + 2 |d| + |r|) <= 4 eps (S + E) for a segment, twice
+// that for the face; the squared norm adds 3.01 eps relative, i.e. 1.51 eps on the distance.  So
+// sqrt(pinned d2) >= |g*| - 16 eps rho (tests/mesh_metrics_reference.py: LOWER_C, checked against float64 there).
+// (2) The computed D is not far ABOVE |g*| - mu.  lo - p is off by eps |lo - p| <= eps rho, the subtraction of mu by
+// as much again, so each computed gap is at most max(g* - mu + 2.01 eps rho, 0); lowering every positive component of
+// a non-negative vector by m' lowers its norm by at least m' (the norm's slope along -(1, 1, 1) is sum g / |g| >= 1);
+// the squared norm adds 1.51 eps rho.  So sqrt(D2) <= |g*| - mu + 3.6 eps rho wherever that is positive, else D2 = 0.
+// (3) Hence D2 > pinned d2 needs mu < 19.6 eps rho, while mu = 2^-11 rho~ = 8192 eps rho~ with the fp32 rho~ within
+// 5 eps of rho: the margin is about 400 times what the argument needs, as the ray code's is generous for its claim.
+// Nothing here depends on the triangle's shape: the one-sided bound (1) holds for slivers and zero-area triangles too.
+// Domain: that of the ray code — finite coordinates of magnitude <= 2^20 for vertices and points, a mesh extent in
+// [2^-20, 2^20]; products of three differences stay below 2^87 and above the subnormals.
 #include <cmath>
 
 #include "common.h"
@@ -126,14 +164,13 @@ __device__ __forceinline__ bool node_hit(const Ray& r, const float4 lo, const fl
   return !(enter > exit) && enter != INFINITY && exit != -INFINITY;
 }
 
-// Walks the tree for one ray: leaf(begin, end) gets the sorted-triangle range of every leaf whose box the ray may meet
-// within [t_min, t_hi()], and returns true to stop.
-template <class Hi, class Leaf>
-__device__ __forceinline__ void traverse(const Bvh& b, const float4* __restrict__ nodes, const Ray& r, float t_min,
-                                         Hi&& t_hi, Leaf&& leaf) {
+// The stackless pre-order walk, shared by the ray queries and the nearest-triangle query: test(k) says whether node k
+// may hold an answer; leaf(begin, end) gets the sorted-triangle range of every leaf that passes, and returns true to stop.
+template <class Test, class Leaf>
+__device__ __forceinline__ void walk(const Bvh& b, Test&& test, Leaf&& leaf) {
   int k = 1;
   do {
-    const bool hit = node_hit(r, nodes[2 * k], nodes[2 * k + 1], t_min, t_hi());
+    const bool hit = test(k);
     if (hit && k < b.leaves) {
       k = 2 * k;
       continue;
@@ -145,6 +182,126 @@ __device__ __forceinline__ void traverse(const Bvh& b, const float4* __restrict_
     k += 1;
     k >>= __builtin_ctz(k);
   } while (k != 1);
+}
+
+// Walks the tree for one ray: leaf(begin, end) gets the sorted-triangle range of every leaf whose box the ray may meet
+// within [t_min, t_hi()], and returns true to stop.
+template <class Hi, class Leaf>
+__device__ __forceinline__ void traverse(const Bvh& b, const float4* __restrict__ nodes, const Ray& r, float t_min,
+                                         Hi&& t_hi, Leaf&& leaf) {
+  walk(b, [&](int k) { return node_hit(r, nodes[2 * k], nodes[2 * k + 1], t_min, t_hi()); }, leaf);
+}
+
+// ---------------------------------------------------------------------------------------- nearest triangle ----
+
+// the clamped segment a + t d, t in [0, 1], against the offset w = p - a: if it is strictly nearer than *best, takes over
+__device__ __forceinline__ void seg_nearest(float wx, float wy, float wz, float dx, float dy, float dz, float& best,
+                                            float& bt) {
+#pragma clang fp contract(off)
+  const float dd = (dx * dx + dy * dy) + dz * dz;
+  const float wd = (wx * dx + wy * dy) + wz * dz;
+  float t = 0.0f;
+  if (dd > 0.0f) {
+    t = wd / dd;  // correctly rounded
+    t = t > 0.0f ? t : 0.0f;  // a NaN (inf / inf cannot occur in the domain) would become 0 as well
+    t = t < 1.0f ? t : 1.0f;
+  }
+  const float rx = wx - t * dx, ry = wy - t * dy, rz = wz - t * dz;
+  const float d2 = (rx * rx + ry * ry) + rz * rz;
+  if (d2 < best) {
+    best = d2;
+    bt = t;
+  }
+}
+
+// the pinned point-triangle distance of the file header: d2, and in (qx, qy, qz), if cp asks for it, the closest point
+__device__ __forceinline__ float tri_nearest(float px, float py, float pz, const float* __restrict__ v, bool cp,
+                                             float& qx, float& qy, float& qz) {
+#pragma clang fp contract(off)
+  const float ax = v[0], ay = v[1], az = v[2], bx = v[3], by = v[4], bz = v[5], cx = v[6], cy = v[7], cz = v[8];
+  const float e1x = bx - ax, e1y = by - ay, e1z = bz - az;
+  const float e2x = cx - ax, e2y = cy - ay, e2z = cz - az;
+  const float e3x = cx - bx, e3y = cy - by, e3z = cz - bz;
+  const float wx = px - ax, wy = py - ay, wz = pz - az;
+  const float zx = px - bx, zy = py - by, zz = pz - bz;
+  float best = INFINITY, t0 = 0.0f, t1 = 0.0f, t2 = 0.0f;
+  seg_nearest(wx, wy, wz, e1x, e1y, e1z, best, t0);  // a -> b
+  float d2 = best;
+  int which = 0;
+  seg_nearest(zx, zy, zz, e3x, e3y, e3z, best, t1);  // b -> c
+  if (best < d2) d2 = best, which = 1;
+  seg_nearest(wx, wy, wz, e2x, e2y, e2z, best, t2);  // a -> c
+  if (best < d2) d2 = best, which = 2;
+  // the face: only where the normal is not 0 and the projection has barycentric coordinates inside
+  const float nx = e1y * e2z - e1z * e2y, ny = e1z * e2x - e1x * e2z, nz = e1x * e2y - e1y * e2x;
+  const float nn = (nx * nx + ny * ny) + nz * nz;
+  float fu = 0.0f, fv = 0.0f;
+  if (nn > 0.0f) {
+    const float mx = wy * e2z - wz * e2y, my = wz * e2x - wx * e2z, mz = wx * e2y - wy * e2x;  // w x e2
+    const float lx = e1y * wz - e1z * wy, ly = e1z * wx - e1x * wz, lz = e1x * wy - e1y * wx;  // e1 x w
+    const float u = ((mx * nx + my * ny) + mz * nz) / nn;
+    const float w = ((lx * nx + ly * ny) + lz * nz) / nn;
+    if (u >= 0.0f && w >= 0.0f && u + w <= 1.0f) {
+      const float rx = (wx - u * e1x) - w * e2x, ry = (wy - u * e1y) - w * e2y, rz = (wz - u * e1z) - w * e2z;
+      const float f2 = (rx * rx + ry * ry) + rz * rz;
+      if (f2 < d2) d2 = f2, which = 3, fu = u, fv = w;
+    }
+  }
+  if (cp) {
+    if (which == 0) qx = ax + t0 * e1x, qy = ay + t0 * e1y, qz = az + t0 * e1z;
+    if (which == 1) qx = bx + t1 * e3x, qy = by + t1 * e3y, qz = bz + t1 * e3z;
+    if (which == 2) qx = ax + t2 * e2x, qy = ay + t2 * e2y, qz = az + t2 * e2z;
+    if (which == 3) qx = (ax + fu * e1x) + fv * e2x, qy = (ay + fu * e1y) + fv * e2y, qz = (az + fu * e1z) + fv * e2z;
+  }
+  return d2;
+}
+
+// squared distance from p to the node's box, each face moved outward by mu; 0 for the box (-inf, +inf) of the slivers
+__device__ __forceinline__ float box_d2(float px, float py, float pz, float mu, const float4 lo, const float4 hi) {
+#pragma clang fp contract(off)
+  const float gx = fmaxf(fmaxf((lo.x - px) - mu, (px - hi.x) - mu), 0.0f);
+  const float gy = fmaxf(fmaxf((lo.y - py) - mu, (py - hi.y) - mu), 0.0f);
+  const float gz = fmaxf(fmaxf((lo.z - pz) - mu, (pz - hi.z) - mu), 0.0f);
+  return (gx * gx + gy * gy) + gz * gz;
+}
+
+__global__ __launch_bounds__(kBlock) void rt_nearest_kernel(Bvh b, const float* __restrict__ tris,
+                                                            const int32_t* __restrict__ order,
+                                                            const float4* __restrict__ nodes,
+                                                            const float* __restrict__ pts, int64_t m,
+                                                            float* __restrict__ out_d2, int32_t* __restrict__ out_id,
+                                                            float* __restrict__ out_point) {
+  for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < m; i += (int64_t)gridDim.x * kBlock) {
+    const float px = pts[3 * i], py = pts[3 * i + 1], pz = pts[3 * i + 2];
+    const float mu = kMargin * (((fabsf(px - b.cx) + fabsf(py - b.cy)) + fabsf(pz - b.cz)) + 3.0f * b.radius);
+    float best = INFINITY, bx = 0.0f, by = 0.0f, bz = 0.0f;
+    int best_id = -1;
+    walk(
+        b,
+        [&](int k) {
+          const float4 lo = nodes[2 * k], hi = nodes[2 * k + 1];
+          if (!(lo.x <= hi.x)) return false;  // empty
+          return !(box_d2(px, py, pz, mu, lo, hi) > best);
+        },
+        [&](int begin, int end) {
+          for (int j = begin; j < end; ++j) {
+            float qx = 0.0f, qy = 0.0f, qz = 0.0f;
+            const float d2 = tri_nearest(px, py, pz, tris + 9 * (int64_t)j, out_point != nullptr, qx, qy, qz);
+            if (d2 <= best) {
+              const int id = order[j];
+              if (d2 < best || best_id < 0 || id < best_id) {
+                best = d2;
+                best_id = id;
+                bx = qx, by = qy, bz = qz;
+              }
+            }
+          }
+          return false;
+        });
+    out_d2[i] = best;
+    out_id[i] = best_id;
+    if (out_point) out_point[3 * i] = bx, out_point[3 * i + 1] = by, out_point[3 * i + 2] = bz;
+  }
 }
 
 __global__ __launch_bounds__(kBlock) void rt_morton_kernel(Bvh b, const float* __restrict__ tris,
@@ -370,6 +527,21 @@ extern "C" int lnrf_rt_occluded(const lnrf_rt_bvh* bvh, const float* sorted_tris
   LNRF_CHECK_ARG(out, "null pointer");
   hipLaunchKernelGGL(rt::rt_occluded_kernel, dim3(rt::grid_for(m)), dim3(rt::kBlock), 0, as_stream(stream), b,
                      sorted_tris, (const float4*)nodes, rays, window, m, out);
+  LNRF_LAUNCH_CHECK();
+  return LNRF_OK;
+}
+
+extern "C" int lnrf_mesh_nearest(const lnrf_rt_bvh* bvh, const float* sorted_tris, const int32_t* order,
+                                 const float* nodes, const float* pts, int64_t m, float* out_d2, int32_t* out_id,
+                                 float* out_point, lnrf_stream_t stream) {
+  rt::Bvh b;
+  int rc = rt::check_bvh(__func__, bvh, &b);
+  if (rc == LNRF_OK) rc = check_query(__func__, sorted_tris, nodes, pts, m);
+  if (rc != LNRF_OK) return rc;
+  if (m == 0) return LNRF_OK;
+  LNRF_CHECK_ARG(order && out_d2 && out_id, "null pointer");
+  hipLaunchKernelGGL(rt::rt_nearest_kernel, dim3(rt::grid_for(m)), dim3(rt::kBlock), 0, as_stream(stream), b,
+                     sorted_tris, order, (const float4*)nodes, pts, m, out_d2, out_id, out_point);
   LNRF_LAUNCH_CHECK();
   return LNRF_OK;
 }

@@ -167,6 +167,11 @@ PROTOTYPES = {
     "lnrf_rt_fit": (c_int32, [POINTER(RtBvh), _P, _P, _P]),
     "lnrf_rt_closest": (c_int32, [POINTER(RtBvh), _P, _P, _P, _P, _P, c_int64, _P, _P, _P]),
     "lnrf_rt_occluded": (c_int32, [POINTER(RtBvh), _P, _P, _P, _P, c_int64, _P, _P]),
+    "lnrf_mesh_nearest": (c_int32, [POINTER(RtBvh), _P, _P, _P, _P, c_int64, _P, _P, _P, _P]),
+    "lnrf_mesh_tri_areas": (c_int32, [_P, c_int64, _P, _P]),
+    "lnrf_mesh_sample_surface": (c_int32, [_P, _P, _P, c_int64, c_int64, c_uint64, c_uint32, _P, _P, _P]),
+    "lnrf_dist_stats_scratch_bytes": (c_int64, [c_int64]),
+    "lnrf_dist_stats_f64": (c_int32, [_P, _P, c_int64, POINTER(ctypes.c_double), c_int32, _P, _P, c_int64, _P]),
     "lnrf_sq_err_scratch_bytes": (c_int64, [c_int64]),
     "lnrf_sq_err_f64": (c_int32, [_P, _P, c_int64, c_int64, _P, _P, _P, c_int64, _P]),
     "lnrf_view_miss_scratch_bytes": (c_int64, [c_int32, c_int32]),

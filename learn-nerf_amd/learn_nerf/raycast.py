@@ -191,7 +191,8 @@ def camera_json(view: CameraView) -> dict:
 
 class TriangleMesh:
     """
-    The triangles [n, 3, 3] (GPU, fp32) in the tree of csrc/raycast.hip, for first-hit and any-hit queries.  leaf_size
+    The triangles [n, 3, 3] (GPU, fp32) in the tree of csrc/raycast.hip, for first-hit and any-hit ray queries, for the
+    nearest-triangle query of a point and for area-weighted surface samples (learn_nerf/mesh_metrics.py).  leaf_size
     forces the triangles per leaf; results do not depend on it.  Input outside the domain stated in the kernel file's
     header (non-finite values, coordinates beyond 2^20, a mesh extent outside [2^-20, 2^20], directions that are not
     unit vectors, NaN windows) raises before any launch.
@@ -289,6 +290,89 @@ class TriangleMesh:
                                          L.ptr(rays), L.ptr(window), m, L.ptr(occ, torch.uint8), L.stream()),
                 "rt_occluded")
         return occ
+
+    def _check_points(self, points: torch.Tensor) -> torch.Tensor:
+        if not isinstance(points, torch.Tensor):
+            raise TypeError(f"expected a torch.Tensor, got {type(points)}")
+        if points.dim() != 2 or points.shape[1] != 3:
+            raise ValueError(f"points: expected shape [m, 3], got {tuple(points.shape)}")
+        if not points.is_cuda:
+            raise RuntimeError("points: the ray caster needs tensors on a ROCm GPU device (no CPU fallback)")
+        points = points.to(F32).contiguous()
+        if points.shape[0]:
+            if not torch.isfinite(points).all():
+                raise ValueError("points: non-finite coordinates")
+            if points.abs().max().item() > MAX_COORD:
+                raise ValueError("points: coordinates beyond 2^20 are outside the ray caster's domain")
+        return points
+
+    def nearest(self, points: torch.Tensor,
+                out: Optional[Tuple[torch.Tensor, ...]] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """(d2 fp32 [m], id int32 [m]) of the triangle nearest to each point of points [m, 3]: the pinned fp32
+        point-triangle distance of csrc/raycast.hip ("Nearest triangle"), squared, the lowest index among equal d2.
+        out: (d2, id) or (d2, id, closest fp32 [m, 3]); with the third tensor the closest point of that triangle is
+        written too, and the three are returned."""
+        points = self._check_points(points)
+        m = points.shape[0]
+        if out is None:
+            out = (torch.empty(m, dtype=F32, device=points.device),
+                   torch.empty(m, dtype=torch.int32, device=points.device))
+        if len(out) not in (2, 3) or out[0].shape != (m,) or out[1].shape != (m,):
+            raise ValueError("out: expected two tensors of shape [m], and optionally one of shape [m, 3]")
+        closest = out[2] if len(out) == 3 else None
+        if closest is not None and tuple(closest.shape) != (m, 3):
+            raise ValueError("out: expected two tensors of shape [m], and optionally one of shape [m, 3]")
+        L.check(L.lib().lnrf_mesh_nearest(ctypes.byref(self.bvh), L.ptr(self.sorted_tris),
+                                          L.ptr(self.order, torch.int32), L.ptr(self.nodes), L.ptr(points), m,
+                                          L.ptr(out[0]), L.ptr(out[1], torch.int32), L.ptr(closest), L.stream()),
+                "mesh_nearest")
+        return tuple(out)
+
+    def tri_areas(self) -> torch.Tensor:
+        """fp32 [n]: the pinned area of every triangle, in the original order."""
+        areas = torch.empty(self.n, dtype=F32, device=self.tris.device)
+        L.check(L.lib().lnrf_mesh_tri_areas(L.ptr(self.tris), self.n, L.ptr(areas), L.stream()), "mesh_tri_areas")
+        return areas
+
+    def surface_cdf(self) -> np.ndarray:
+        """float64 [n] (host): the running sum of the pinned areas over the SORTED triangles, added one by one in
+        float64, so that it is the same array on every device."""
+        areas = torch.empty(self.n, dtype=F32, device=self.tris.device)
+        L.check(L.lib().lnrf_mesh_tri_areas(L.ptr(self.sorted_tris), self.n, L.ptr(areas), L.stream()),
+                "mesh_tri_areas")
+        return np.cumsum(areas.cpu().numpy().astype(np.float64))
+
+    def sample_surface(self, count: int, seed: int, stream_id: int = 0,
+                       cdf: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """(points fp32 [count, 3], id int32 [count]): stratified samples of the surface in proportion to area, and the
+        original index of each sample's triangle (csrc/mesh_metrics.hip fixes every bit given the cdf).  Sample i draws
+        elements 3i, 3i + 1, 3i + 2 of Philox stream `stream_id` under `seed`.  Samples follow the tree's sorted order
+        of the triangles, so neighbours in the array are neighbours in space.  cdf: a device float64 [n] running sum
+        of areas over self.sorted_tris to use in place of surface_cdf()."""
+        count = int(count)
+        if count < 0:
+            raise ValueError(f"count must not be negative, got {count}")
+        dev = self.tris.device
+        if cdf is None:
+            cdf = torch.from_numpy(self.surface_cdf()).to(dev)
+        if not cdf.is_cuda:
+            raise RuntimeError("cdf: the ray caster needs tensors on a ROCm GPU device (no CPU fallback)")
+        if cdf.dtype != torch.float64 or tuple(cdf.shape) != (self.n,):
+            raise ValueError(f"cdf: expected float64 of shape [{self.n}]")
+        cdf = cdf.contiguous()
+        total = float(cdf[-1].item())
+        if not (total > 0 and math.isfinite(total)):
+            raise ValueError("the mesh has zero total area: nothing to sample")
+        if self.n > 1 and bool((cdf[1:] < cdf[:-1]).any().item()):
+            raise ValueError("cdf: must be non-decreasing")
+        pts = torch.empty((count, 3), dtype=F32, device=dev)
+        ids = torch.empty(count, dtype=torch.int32, device=dev)
+        L.check(L.lib().lnrf_mesh_sample_surface(L.ptr(self.sorted_tris), L.ptr(self.order, torch.int32),
+                                                 L.ptr(cdf, torch.float64), self.n, count,
+                                                 int(seed) & 0xFFFFFFFFFFFFFFFF, int(stream_id) & 0xFFFFFFFF,
+                                                 L.ptr(pts), L.ptr(ids, torch.int32), L.stream()),
+                "mesh_sample_surface")
+        return pts, ids
 
     def shade(self, rays: torch.Tensor, t: torch.Tensor, idx: torch.Tensor, lights, color) -> torch.Tensor:
         """uint8 [m, 4]: the RGBA of the module docstring for the rays and their closest() result."""
