@@ -834,6 +834,57 @@ int lnrf_tsdf_volume(const float* sum_t, const int32_t* n_obs, const uint8_t* be
 int lnrf_tsdf_vertex_colors(const float* verts, int64_t n, int64_t nx, int64_t ny, int64_t nz, const int32_t* rgb_sum,
                             const int32_t* n_col, float* rgb_out, int32_t* n_missing, lnrf_stream_t stream);
 
+/* ----------------------------------------------------- mesh simplification ---- */
+
+/* Vertex clustering with quadric error metrics (Lindstrom 2000) on a grid of cubic cells (additive; csrc/simplify.hip,
+ * whose header comment fixes the conventions and the order of the fold, and csrc/simplify_geom.h for the arithmetic,
+ * operation by operation; learn_nerf/simplify.py drives the passes).  Everything is defined on triangle corners:
+ * entry e = 3t + k is corner k of triangle t of tris [n_tris, 3, 3] fp32, n_tris <= INT32_MAX / 3 (LNRF_ERR_SHAPE
+ * beyond).  Grid: origin lo (at or below every corner), inv_h = the fp32 rounding of 1 / h, dims each >= 1 with fewer
+ * than 2^31 cells in all (LNRF_ERR_SHAPE; checked before any pointer is looked at).  No entry point allocates, copies
+ * or synchronises; the only atomics are integer adds. */
+typedef struct lnrf_simp_grid {
+  float lo[3];
+  float inv_h;
+  int32_t dims[3];
+  int32_t pad_;
+} lnrf_simp_grid;
+
+#define LNRF_SIMP_MEAN 0
+#define LNRF_SIMP_QUADRIC 1
+
+/* keys [n] (device int32): (cx*ny + cy)*nz + cz of each point of pts [n, 3], c_a = min(n_a - 1,
+ * (int)floorf((p_a - lo_a) * inv_h)), every fp32 operation rounded once. */
+int lnrf_simp_cell_keys(const lnrf_simp_grid* grid, const float* pts, int64_t n, int32_t* keys, lnrf_stream_t stream);
+/* *count (one device int64, which the caller clears) += the triangles whose three corners have three distinct keys. */
+int lnrf_simp_count_faces(const lnrf_simp_grid* grid, const float* tris, int64_t n_tris, int64_t* count,
+                          lnrf_stream_t stream);
+/* (host) the segment length above which shape 0 of lnrf_simp_accumulate gives a segment to a wave. */
+int32_t lnrf_simp_long_segment(void);
+/* The per-cell sums.  keys [3 n_tris]: lnrf_simp_cell_keys of the corners; order [3 n_tris] int32: the entries stably
+ * sorted by key; seg_start [n_cells + 1] int32: the first sorted entry of each occupied cell, [n_cells] = 3 n_tris.
+ * colors (nullable, with col_sums): uint8 [3 n_tris, 3], one RGB per corner.  Per cell: counts int32 = its corners,
+ * sums double [13] = the corner position sum and the 10 coefficients (A upper triangle, b, c) of the area-weighted plane
+ * quadrics of its triangles, each triangle once, folded in fp64 in the fixed order of csrc/simplify.hip; col_sums int64
+ * [3].  shape: 0 = a 16-lane group per short segment and a wave per long one, 1 = groups only, 2 = waves only; the
+ * results do not depend on it.  Entries outside [0, 3 n_tris) and segment bounds outside the array are skipped. */
+int lnrf_simp_accumulate(const float* tris, int64_t n_tris, const int32_t* keys, const int32_t* order,
+                         const int32_t* seg_start, int64_t n_cells, const uint8_t* colors, int32_t shape,
+                         int32_t* counts, double* sums, int64_t* col_sums, lnrf_stream_t stream);
+/* verts fp32 [n_cells, 3]: the vertex of each occupied cell (cell_keys [n_cells] int32) from its counts and sums:
+ * LNRF_SIMP_MEAN = the corner mean x0, LNRF_SIMP_QUADRIC = x0 + A^+ (b - A x0) by a cyclic Jacobi eigen-decomposition
+ * in fp64 with eigenvalues at or below 1e-3 of the largest dropped; fell_back uint8 [n_cells] = 1 where the result was
+ * not finite or further than h from the cell centre in the max norm and x0 was returned instead.  h: the cell edge in
+ * fp64.  colors (nullable, with col_sums) uint8 [n_cells, 3] = floor(sum / count + 0.5). */
+int lnrf_simp_place(const lnrf_simp_grid* grid, double h, const int32_t* cell_keys, const int32_t* counts,
+                    const double* sums, const int64_t* col_sums, int64_t n_cells, int32_t placement, float* verts,
+                    uint8_t* colors, uint8_t* fell_back, lnrf_stream_t stream);
+/* *count (one device int64, which the caller clears) += the faces [n_faces, 3] (int32 into verts [n_verts, 3]) whose
+ * fp64 normal has a negative dot product with that of their input triangle tris[face_src[f]].  Faces that name a
+ * triangle or a vertex out of range are skipped. */
+int lnrf_simp_flipped(const float* tris, int64_t n_tris, const int32_t* face_src, const int32_t* faces,
+                      int64_t n_faces, const float* verts, int64_t n_verts, int64_t* count, lnrf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -47,6 +47,10 @@ class RtBvh(ctypes.Structure):
                 ("leaf_size", c_int32), ("pad_", c_int32)]
 
 
+class SimpGrid(ctypes.Structure):
+    _fields_ = [("lo", c_float * 3), ("inv_h", c_float), ("dims", c_int32 * 3), ("pad_", c_int32)]
+
+
 _P = c_void_p
 _F3 = POINTER(c_float)
 
@@ -195,6 +199,13 @@ PROTOTYPES = {
                                       c_int32, _P, _P, _P, _P, _P, _P]),
     "lnrf_tsdf_volume": (c_int32, [_P, _P, _P, c_int64, c_int64, c_int64, c_int32, _P, _P]),
     "lnrf_tsdf_vertex_colors": (c_int32, [_P, c_int64, c_int64, c_int64, c_int64, _P, _P, _P, _P, _P]),
+    "lnrf_simp_cell_keys": (c_int32, [POINTER(SimpGrid), _P, c_int64, _P, _P]),
+    "lnrf_simp_count_faces": (c_int32, [POINTER(SimpGrid), _P, c_int64, _P, _P]),
+    "lnrf_simp_long_segment": (c_int32, []),
+    "lnrf_simp_accumulate": (c_int32, [_P, c_int64, _P, _P, _P, c_int64, _P, c_int32, _P, _P, _P, _P]),
+    "lnrf_simp_place": (c_int32, [POINTER(SimpGrid), ctypes.c_double, _P, _P, _P, _P, c_int64, c_int32, _P, _P, _P,
+                                  _P]),
+    "lnrf_simp_flipped": (c_int32, [_P, c_int64, _P, _P, c_int64, _P, c_int64, _P, _P]),
 }
 
 _lib = None

@@ -636,3 +636,72 @@ def view_miss_stats_(view, image_u8: torch.Tensor, bbox_min: Sequence[float], bb
         float(min_t_range), float(epsilon), L.ptr(miss, torch.uint8), L.ptr(stats, torch.int64),
         L.ptr(scratch, torch.uint8), nbytes, L.stream()), "view_miss_stats")
     return stats
+
+
+# ---------------------------------------------------------------- mesh simplification
+
+SIMP_PLACEMENTS = {"mean": 0, "quadric": 1}  # LNRF_SIMP_MEAN, LNRF_SIMP_QUADRIC
+SIMP_SHAPES = {"auto": 0, "groups": 1, "waves": 2}  # launch shapes of lnrf_simp_accumulate: same bits
+
+
+def simp_grid(lo: Sequence[float], inv_h: float, dims: Sequence[int]) -> "L.SimpGrid":
+    return L.SimpGrid(L.f3(lo), float(inv_h), (ctypes.c_int32 * 3)(*[int(d) for d in dims]), 0)
+
+
+def simp_cell_keys(grid, pts: torch.Tensor) -> torch.Tensor:
+    """int32 [n]: the cell key of each point of pts [n, 3] (lnrf_simp_cell_keys)."""
+    keys = torch.empty(pts.shape[0], dtype=torch.int32, device=_dev(pts))
+    L.check(L.lib().lnrf_simp_cell_keys(ctypes.byref(grid), L.ptr(pts), pts.shape[0], L.ptr(keys, torch.int32),
+                                        L.stream()), "simp_cell_keys")
+    return keys
+
+
+def simp_count_faces_(grid, tris: torch.Tensor, count: torch.Tensor) -> torch.Tensor:
+    """count (one int64 element) += the triangles of tris [F, 3, 3] with three distinct cells (lnrf_simp_count_faces)."""
+    if count.numel() != 1:
+        raise ValueError("simp_count_faces_: count must be one int64 element")
+    L.check(L.lib().lnrf_simp_count_faces(ctypes.byref(grid), L.ptr(tris), tris.shape[0], L.ptr(count, torch.int64),
+                                          L.stream()), "simp_count_faces")
+    return count
+
+
+def simp_accumulate(tris: torch.Tensor, keys: torch.Tensor, order: torch.Tensor, seg_start: torch.Tensor,
+                    colors: Optional[torch.Tensor] = None, shape: str = "auto"):
+    """(counts int32 [C], sums float64 [C, 13], colour sums int64 [C, 3] or None) of the C occupied cells whose
+    segments seg_start [C + 1] delimits in the sorted entries `order` (lnrf_simp_accumulate)."""
+    n_cells = seg_start.numel() - 1
+    dev = _dev(tris)
+    counts = torch.empty(n_cells, dtype=torch.int32, device=dev)
+    sums = torch.empty((n_cells, 13), dtype=torch.float64, device=dev)
+    col_sums = None if colors is None else torch.empty((n_cells, 3), dtype=torch.int64, device=dev)
+    L.check(L.lib().lnrf_simp_accumulate(
+        L.ptr(tris), tris.shape[0], L.ptr(keys, torch.int32), L.ptr(order, torch.int32),
+        L.ptr(seg_start, torch.int32), n_cells, L.ptr(colors, torch.uint8), SIMP_SHAPES[shape],
+        L.ptr(counts, torch.int32), L.ptr(sums, torch.float64), L.ptr(col_sums, torch.int64), L.stream()),
+        "simp_accumulate")
+    return counts, sums, col_sums
+
+
+def simp_place(grid, h: float, cell_keys: torch.Tensor, counts: torch.Tensor, sums: torch.Tensor,
+               col_sums: Optional[torch.Tensor], placement: str):
+    """(vertices fp32 [C, 3], colours uint8 [C, 3] or None, fell back uint8 [C]) of the occupied cells
+    (lnrf_simp_place)."""
+    n_cells = cell_keys.numel()
+    dev = _dev(sums)
+    verts = torch.empty((n_cells, 3), dtype=F32, device=dev)
+    colors = None if col_sums is None else torch.empty((n_cells, 3), dtype=torch.uint8, device=dev)
+    fell_back = torch.empty(n_cells, dtype=torch.uint8, device=dev)
+    L.check(L.lib().lnrf_simp_place(
+        ctypes.byref(grid), float(h), L.ptr(cell_keys, torch.int32), L.ptr(counts, torch.int32),
+        L.ptr(sums, torch.float64), L.ptr(col_sums, torch.int64), n_cells, SIMP_PLACEMENTS[placement], L.ptr(verts),
+        L.ptr(colors, torch.uint8), L.ptr(fell_back, torch.uint8), L.stream()), "simp_place")
+    return verts, colors, fell_back
+
+
+def simp_flipped(tris: torch.Tensor, face_src: torch.Tensor, faces: torch.Tensor, verts: torch.Tensor) -> torch.Tensor:
+    """One int64 element: the output faces whose normal opposes their input triangle's (lnrf_simp_flipped)."""
+    count = torch.zeros(1, dtype=torch.int64, device=_dev(tris))
+    L.check(L.lib().lnrf_simp_flipped(L.ptr(tris), tris.shape[0], L.ptr(face_src, torch.int32),
+                                      L.ptr(faces, torch.int32), faces.shape[0], L.ptr(verts), verts.shape[0],
+                                      L.ptr(count, torch.int64), L.stream()), "simp_flipped")
+    return count

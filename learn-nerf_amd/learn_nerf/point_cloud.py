@@ -304,18 +304,21 @@ def write_colored_obj(path: str, verts, faces, colors) -> None:
 
 def write_ply(path: str, verts, colors, faces=None) -> None:
     """Binary little-endian PLY: float32 x y z and uint8 red green blue per vertex, then (when there are any) faces as
-    a uchar count of 3 and three int32 vertex indices.  For the mesh and for a bare cloud."""
+    a uchar count of 3 and three int32 vertex indices.  For the mesh and for a bare cloud.  colors = None leaves the
+    colour properties out."""
     verts = np.asarray(verts, dtype=np.float32).reshape(-1, 3)
     faces = np.zeros((0, 3), np.int32) if faces is None else np.asarray(faces, dtype=np.int32).reshape(-1, 3)
     header = ["ply", "format binary_little_endian 1.0", f"element vertex {len(verts)}", "property float x",
-              "property float y", "property float z", "property uchar red", "property uchar green",
-              "property uchar blue"]
+              "property float y", "property float z"]
+    if colors is not None:
+        header += ["property uchar red", "property uchar green", "property uchar blue"]
     if len(faces):
         header += [f"element face {len(faces)}", "property list uchar int vertex_indices"]
     header.append("end_header")
-    vrec = np.zeros(len(verts), dtype=[("xyz", "<f4", (3,)), ("rgb", "u1", (3,))])
+    vrec = np.zeros(len(verts), dtype=[("xyz", "<f4", (3,))] + ([("rgb", "u1", (3,))] if colors is not None else []))
     vrec["xyz"] = verts
-    vrec["rgb"] = _rgb8(colors).reshape(-1, 3)
+    if colors is not None:
+        vrec["rgb"] = _rgb8(colors).reshape(-1, 3)
     frec = np.zeros(len(faces), dtype=[("n", "u1"), ("idx", "<i4", (3,))])
     frec["n"] = 3
     frec["idx"] = faces

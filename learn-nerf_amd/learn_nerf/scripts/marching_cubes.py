@@ -6,7 +6,8 @@ Deliberate differences: a binary STL writer that works (the reference's cannot r
 an output extension other than .obj / .stl and for a grid where no occupancy exceeds the threshold, and one additive
 flag, --world_coords.  Additive as well: --min_component / --keep_largest / --connectivity remove floaters, the connected
 components of {occupancy > threshold} that are small or not among the largest (learn_nerf/components.py), before the
-surface is extracted; without them nothing changes.
+surface is extracted; without them nothing changes.  --target_faces / --simplify_grid simplify the extracted mesh by
+quadric vertex clustering (learn_nerf/simplify.py) before the frame transform; without them nothing changes either.
 """
 import argparse
 import sys
@@ -36,6 +37,10 @@ def build_parser() -> argparse.ArgumentParser:
                         help="(additive) keep only this many of the largest connected components")
     parser.add_argument("--connectivity", type=int, default=26, choices=(6, 26),
                         help="(additive) grid points are joined through faces (6) or faces, edges and corners (26)")
+    parser.add_argument("--target_faces", type=int, default=None,
+                        help="(additive) simplify the mesh to at most this many faces")
+    parser.add_argument("--simplify_grid", type=int, default=None,
+                        help="(additive) simplify the mesh on a grid of this many cells along its longest axis")
     parser.add_argument("metadata_json", type=str)
     parser.add_argument("output_obj", type=str, help="output mesh, .obj or .stl")
     return parser
@@ -51,6 +56,10 @@ def main(argv=None):
         parser.error("--resolution must be at least 2 and --batch_size positive")
     if args.min_component < 1 or (args.keep_largest is not None and args.keep_largest < 1):
         parser.error("--min_component and --keep_largest must be at least 1")
+    if args.target_faces is not None and args.simplify_grid is not None:
+        parser.error("give --target_faces or --simplify_grid, not both")
+    if any(v is not None and v < 1 for v in (args.target_faces, args.simplify_grid)):
+        parser.error("--target_faces and --simplify_grid must be at least 1")
 
     print("loading metadata...")
     metadata = ModelMetadata.from_json(args.metadata_json)
@@ -72,6 +81,15 @@ def main(argv=None):
             sys.exit(f"no surface: the filter removed all {found['components']} components")
     if faces.shape[0] == 0:
         sys.exit(f"no surface: no occupancy exceeds the threshold {args.threshold} (largest occupancy {largest:.6g})")
+    if args.target_faces is not None or args.simplify_grid is not None:
+        from learn_nerf.simplify import format_info, simplify
+
+        try:
+            simple = simplify(verts, faces, target_faces=args.target_faces, grid=args.simplify_grid)
+        except ValueError as err:
+            sys.exit(f"no surface after simplification: {err}")
+        print("simplified: " + " ".join(format_info(simple.info)))
+        verts, faces = simple.verts, simple.faces
     verts, faces = verts.cpu().numpy(), faces.cpu().numpy()
     if args.world_coords:
         verts = world_frame(verts, *box)
