@@ -885,6 +885,65 @@ int lnrf_simp_place(const lnrf_simp_grid* grid, double h, const int32_t* cell_ke
 int lnrf_simp_flipped(const float* tris, int64_t n_tris, const int32_t* face_src, const int32_t* faces,
                       int64_t n_faces, const float* verts, int64_t n_verts, int64_t* count, lnrf_stream_t stream);
 
+/* ---------------------------------------------------------- texture baking ---- */
+
+/* A texture atlas with one right-angled patch per triangle and the bake of dataset views into it (additive;
+ * csrc/texture.hip, the bake kernel in csrc/raycast.hip, and csrc/tex_geom.h for the layout, the no-bleed argument and
+ * the arithmetic, operation by operation; learn_nerf/texture.py drives the passes).  The texture is size x size texels,
+ * texel (x, y) has linear index y * size + x; faces go two to a cell of cell x cell texels, cells_per_row =
+ * ceil(sqrt(ceil(faces / 2))), size = cells_per_row * cell, 6 <= cell <= 256, size <= 2^15, faces >= 1: anything else
+ * is LNRF_ERR_SHAPE (checked before any pointer is looked at).  tris [faces, 3, 3] fp32 in the caller's face order.
+ * No entry point allocates, copies or synchronises; the only atomic is the integer add of lnrf_tex_fill. */
+typedef struct lnrf_tex_atlas {
+  int32_t faces, cells_per_row, cell, size;
+} lnrf_tex_atlas;
+
+typedef struct lnrf_tex_view {
+  float origin[3];
+  float inv[9]; /* rows of M^-1, M = [tan(x_fov/2) x_axis | tan(y_fov/2) y_axis | camera_direction] (columns) */
+  int32_t width, height; /* each >= 2 */
+  int64_t pixel_offset;  /* this view's first pixel in `rgba` (uint8 [.., 4]), in pixels */
+} lnrf_tex_view;
+
+/* Per texel: face int32 [size^2] (-1: none), position fp32 [size^2, 3] (the clamped surface point), normal fp32
+ * [size^2, 3] (unit, geometric; (0, 0, 0) marks a zero-area face), bary fp32 [size^2, 3] in the face's vertex order.
+ * Texels without a face get zeros.  Any output but face may be NULL. */
+int lnrf_tex_texels(const lnrf_tex_atlas* atlas, const float* tris, int32_t* face, float* position, float* normal,
+                    float* bary, lnrf_stream_t stream);
+/* uv fp32 [m, 2] (texels; OBJ coordinates are u / size, 1 - v / size) of the surface points points [m, 3] of the faces
+ * ids [m]: projected onto the face's plane, the barycentrics clamped into the triangle.  An id outside [0, faces)
+ * gives NaN. */
+int lnrf_tex_uv(const lnrf_tex_atlas* atlas, const float* tris, const float* points, const int32_t* ids, int64_t m,
+                float* uv, lnrf_stream_t stream);
+/* out fp32 [m, 3]: the bilinear sample at uv [m, 2] (texels) of texture [height, width, 3], uint8 (is_float = 0) or
+ * fp32; nested lerps a + t * (b - a), indices clamped at the border, a texel of weight 0 is not read.  height and
+ * width in [1, 2^15] (LNRF_ERR_SHAPE). */
+int lnrf_tex_sample(const void* texture, int32_t is_float, int64_t height, int64_t width, const float* uv, int64_t m,
+                    float* out, lnrf_stream_t stream);
+/* Adds views[0 .. n_views) (a device array), in order, to state fp32 [size^2, 4] = (sum w r, sum w g, sum w b, sum w),
+ * caller-owned and zeroed before the first view; r, g, b in 0 .. 255.  A view contributes to a texel of a face with a
+ * normal when the cosine between the normal and the direction to the camera exceeds cos_max, the bilinear footprint of
+ * the projection lies inside the image, its pixels all have alpha >= 128, and the ray from the point (moved by offset
+ * along the normal) to the camera hits no triangle of the tree (bvh, sorted_tris, nodes: lnrf_rt_fit of the same
+ * triangles); weight = cosine^power.  rgba: the packed uint8 [.., 4] images that the descriptors index (not checked:
+ * the descriptors are on the device).  0 <= power <= 64, offset >= 0 and finite, cos_max finite (LNRF_ERR_ARG).  One
+ * lane owns a texel: no atomics, and the same bits however the views are split over calls.  n_views = 0 launches
+ * nothing. */
+int lnrf_tex_bake_views(const lnrf_rt_bvh* bvh, const float* sorted_tris, const float* nodes,
+                        const lnrf_tex_atlas* atlas, const float* tris, const lnrf_tex_view* views, int64_t n_views,
+                        const uint8_t* rgba, float cos_max, int32_t power, float offset, float* state,
+                        lnrf_stream_t stream);
+/* rgb uint8 [size^2, 3] and seen uint8 [size^2] from the state: seen = sum w > 0, byte = floor(255 * clamp((sum w c /
+ * sum w) / 255, 0, 1) + 0.5); an unseen texel gets (unseen_r, unseen_g, unseen_b), each in [0, 255]. */
+int lnrf_tex_resolve(const lnrf_tex_atlas* atlas, const float* state, int32_t unseen_r, int32_t unseen_g,
+                     int32_t unseen_b, uint8_t* rgb, uint8_t* seen, lnrf_stream_t stream);
+/* One Jacobi pass from (rgb_in, seen_in) to (rgb_out, seen_out), distinct buffers: a texel with seen == 0 and a face
+ * takes the mean (integers, round half up; order left, right, up, down) of its 4-neighbours that have seen != 0 and the
+ * same face, and seen = 2; every other texel is copied.  *filled (one device int32, which the caller clears) += the
+ * texels filled. */
+int lnrf_tex_fill(const lnrf_tex_atlas* atlas, const uint8_t* rgb_in, const uint8_t* seen_in, uint8_t* rgb_out,
+                  uint8_t* seen_out, int32_t* filled, lnrf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

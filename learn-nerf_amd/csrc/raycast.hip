@@ -84,9 +84,14 @@
 // Nothing here depends on the triangle's shape: the one-sided bound (1) holds for slivers and zero-area triangles too.
 // Domain: that of the ray code — finite coordinates of magnitude <= 2^20 for vertices and points, a mesh extent in
 // [2^-20, 2^20]; products of three differences stay below 2^87 and above the subnormals.
+//
+// Texture bake (lnrf_tex_bake_views; learn_nerf/texture.py): the any-hit query above, started per (texel, view) from
+// inside the kernel instead of from a ray array; tex_geom.h fixes its arithmetic, the section further down the launch.
 #include <cmath>
+#include <limits.h>
 
 #include "common.h"
+#include "tex_geom.h"
 
 namespace lnrf {
 namespace rt {
@@ -415,6 +420,88 @@ __global__ __launch_bounds__(kBlock) void rt_occluded_kernel(Bvh b, const float*
   }
 }
 
+// ------------------------------------------------------------------------------------------- texture bake ----
+// lnrf_tex_bake_views (tex_geom.h "Bake" fixes every operation; learn_nerf/texture.py drives it).  One lane per texel,
+// a wave per tile of 8 x 8 texels, so that a wave's lanes share one to four faces: their points project to neighbouring
+// pixels and their shadow rays walk the same nodes.  The lane computes its point and normal once, loads its state once,
+// walks the launch's views in order with the state in registers and stores it once; the descriptors are read at a
+// wave-uniform index.  Per view the tests run cheapest first (facing, projection and footprint, alpha: arithmetic and
+// four byte gathers) and only a (texel, view) pair that survives them starts a traversal.  No atomics, no scratch: a
+// texel's result depends on the sequence of views alone, not on the launch geometry and not on how the views are split
+// over launches (the state between two launches is exactly the registers' content).
+constexpr int kTexTile = 8;
+static_assert(kTexTile * kTexTile == kWave, "one texel per lane");
+
+__global__ __launch_bounds__(kBlock) void tex_bake_views_kernel(Bvh b, const float* __restrict__ sorted_tris,
+                                                                const float4* __restrict__ nodes, tex::Atlas at,
+                                                                const float* __restrict__ tris,
+                                                                const lnrf_tex_view* __restrict__ views, int n_views,
+                                                                const uint8_t* __restrict__ rgba, float cos_max,
+                                                                int power, float offset, float4* __restrict__ state) {
+#pragma clang fp contract(off)
+  const int lane = threadIdx.x & (kWave - 1);
+  const int tiles_x = (at.size + kTexTile - 1) / kTexTile;
+  const int tiles = tiles_x * tiles_x;
+  const int first = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * (kBlock / kWave) + threadIdx.x / kWave));
+  for (int tile = first; tile < tiles; tile += gridDim.x * (kBlock / kWave)) {
+    const int x = (tile % tiles_x) * kTexTile + (lane & (kTexTile - 1)), y = (tile / tiles_x) * kTexTile + lane / kTexTile;
+    if (x >= at.size || y >= at.size) continue;
+    int ci, cj;
+    const int f = tex::texel_face(at, x, y, &ci, &cj);
+    if (f < 0) continue;
+    const tex::Frame fr = tex::face_frame(tris + 9 * (int64_t)f);
+    if (fr.degenerate) continue;
+    float bb, bc, p[3], n[3];
+    tex::texel_bary(at.cell, f & 1, ci, cj, bb, bc);
+    tex::surface_point(fr, bb, bc, p);
+    tex::unit_normal(fr, n);
+    const float start[3] = {p[0] + offset * n[0], p[1] + offset * n[1], p[2] + offset * n[2]};
+    const int64_t o = (int64_t)y * at.size + x;
+    float4 st = state[o];
+    for (int v = 0; v < n_views; ++v) {
+      const lnrf_tex_view& view = views[v];
+      const float vx = view.origin[0] - p[0], vy = view.origin[1] - p[1], vz = view.origin[2] - p[2];
+      const float dist = sqrtf((vx * vx + vy * vy) + vz * vz);
+      if (!(dist > 0.0f)) continue;
+      const float lx = vx / dist, ly = vy / dist, lz = vz / dist;
+      const float cosv = (n[0] * lx + n[1] * ly) + n[2] * lz;
+      if (!(cosv > cos_max)) continue;
+      float xf, yf;
+      if (!tex::project(view, p, xf, yf) || !tex::footprint_inside(view, xf, yf)) continue;
+      int i0, i1, j0, j1;
+      float tx, ty;
+      tex::tap_at(xf, view.width, i0, i1, tx);
+      tex::tap_at(yf, view.height, j0, j1, ty);
+      const uchar4* __restrict__ image = (const uchar4*)rgba + view.pixel_offset;
+      const uchar4 c00 = image[(int64_t)j0 * view.width + i0], c10 = image[(int64_t)j0 * view.width + i1];
+      const uchar4 c01 = image[(int64_t)j1 * view.width + i0], c11 = image[(int64_t)j1 * view.width + i1];
+      if (c00.w < 128 || c10.w < 128 || c01.w < 128 || c11.w < 128) continue;
+      Ray r;
+      r.ox = start[0], r.oy = start[1], r.oz = start[2], r.dx = lx, r.dy = ly, r.dz = lz;
+      r.ix = 1.0f / lx, r.iy = 1.0f / ly, r.iz = 1.0f / lz;
+      r.mu = kMargin * (((fabsf(r.ox - b.cx) + fabsf(r.oy - b.cy)) + fabsf(r.oz - b.cz)) + 3.0f * b.radius);
+      bool any = false;
+      traverse(
+          b, nodes, r, 0.0f, [&]() { return dist; },
+          [&](int begin, int end) {
+            for (int j = begin; j < end && !any; ++j) {
+              float t;
+              any = tri_test(r.ox, r.oy, r.oz, r.dx, r.dy, r.dz, sorted_tris + 9 * (int64_t)j, 0.0f, dist, &t);
+            }
+            return any;
+          });
+      if (any) continue;
+      float w = 1.0f;
+      for (int k = 0; k < power; ++k) w = w * cosv;
+      st.x = st.x + w * tex::bilerp((float)c00.x, (float)c10.x, (float)c01.x, (float)c11.x, tx, ty);
+      st.y = st.y + w * tex::bilerp((float)c00.y, (float)c10.y, (float)c01.y, (float)c11.y, tx, ty);
+      st.z = st.z + w * tex::bilerp((float)c00.z, (float)c10.z, (float)c01.z, (float)c11.z, tx, ty);
+      st.w = st.w + w;
+    }
+    state[o] = st;
+  }
+}
+
 static int64_t leaves_for(int64_t n, int32_t leaf) {
   int64_t leaves = 1;
   while (leaves * leaf < n) leaves *= 2;
@@ -542,6 +629,39 @@ extern "C" int lnrf_mesh_nearest(const lnrf_rt_bvh* bvh, const float* sorted_tri
   LNRF_CHECK_ARG(order && out_d2 && out_id, "null pointer");
   hipLaunchKernelGGL(rt::rt_nearest_kernel, dim3(rt::grid_for(m)), dim3(rt::kBlock), 0, as_stream(stream), b,
                      sorted_tris, order, (const float4*)nodes, pts, m, out_d2, out_id, out_point);
+  LNRF_LAUNCH_CHECK();
+  return LNRF_OK;
+}
+
+extern "C" int lnrf_tex_bake_views(const lnrf_rt_bvh* bvh, const float* sorted_tris, const float* nodes,
+                                   const lnrf_tex_atlas* atlas, const float* tris, const lnrf_tex_view* views,
+                                   int64_t n_views, const uint8_t* rgba, float cos_max, int32_t power, float offset,
+                                   float* state, lnrf_stream_t stream) {
+  if (!tex::atlas_ok(atlas)) {
+    set_error("%s: the atlas needs faces >= 1, cells_per_row = ceil(sqrt(ceil(faces / 2))), %d <= cell <= %d and "
+              "size = cells_per_row * cell <= %d",
+              __func__, tex::kMinCell, tex::kMaxCell, tex::kMaxSize);
+    return LNRF_ERR_SHAPE;
+  }
+  if (n_views < 0 || n_views > INT32_MAX) {
+    set_error("%s: n_views = %lld outside [0, INT32_MAX]", __func__, (long long)n_views);
+    return LNRF_ERR_SHAPE;
+  }
+  rt::Bvh b;
+  const int rc = rt::check_bvh(__func__, bvh, &b);
+  if (rc != LNRF_OK) return rc;
+  LNRF_CHECK_ARG(std::isfinite(cos_max), "cos_max must be finite");
+  LNRF_CHECK_ARG(power >= 0 && power <= 64, "power must lie in [0, 64]");
+  LNRF_CHECK_ARG(offset >= 0.0f && std::isfinite(offset), "offset must be finite and not negative");
+  LNRF_CHECK_ARG(sorted_tris && nodes && tris && state, "null pointer");
+  LNRF_CHECK_ARG(((uintptr_t)nodes & 15) == 0 && ((uintptr_t)state & 15) == 0, "nodes and state must be 16-byte aligned");
+  if (n_views == 0) return LNRF_OK;
+  LNRF_CHECK_ARG(views && rgba, "null pointer");
+  LNRF_CHECK_ARG(((uintptr_t)rgba & 3) == 0 && ((uintptr_t)views & 7) == 0, "rgba must be 4-byte, views 8-byte aligned");
+  const int64_t tiles_x = (atlas->size + rt::kTexTile - 1) / rt::kTexTile;
+  hipLaunchKernelGGL(rt::tex_bake_views_kernel, dim3(rt::grid_for(tiles_x * tiles_x * kWave)), dim3(rt::kBlock), 0,
+                     as_stream(stream), b, sorted_tris, (const float4*)nodes, *atlas, tris, views, (int)n_views, rgba,
+                     cos_max, (int)power, offset, (float4*)state);
   LNRF_LAUNCH_CHECK();
   return LNRF_OK;
 }

@@ -51,6 +51,10 @@ class SimpGrid(ctypes.Structure):
     _fields_ = [("lo", c_float * 3), ("inv_h", c_float), ("dims", c_int32 * 3), ("pad_", c_int32)]
 
 
+class TexAtlas(ctypes.Structure):
+    _fields_ = [("faces", c_int32), ("cells_per_row", c_int32), ("cell", c_int32), ("size", c_int32)]
+
+
 _P = c_void_p
 _F3 = POINTER(c_float)
 
@@ -206,6 +210,13 @@ PROTOTYPES = {
     "lnrf_simp_place": (c_int32, [POINTER(SimpGrid), ctypes.c_double, _P, _P, _P, _P, c_int64, c_int32, _P, _P, _P,
                                   _P]),
     "lnrf_simp_flipped": (c_int32, [_P, c_int64, _P, _P, c_int64, _P, c_int64, _P, _P]),
+    "lnrf_tex_texels": (c_int32, [POINTER(TexAtlas), _P, _P, _P, _P, _P, _P]),
+    "lnrf_tex_uv": (c_int32, [POINTER(TexAtlas), _P, _P, _P, c_int64, _P, _P]),
+    "lnrf_tex_sample": (c_int32, [_P, c_int32, c_int64, c_int64, _P, c_int64, _P, _P]),
+    "lnrf_tex_bake_views": (c_int32, [POINTER(RtBvh), _P, _P, POINTER(TexAtlas), _P, _P, c_int64, _P, c_float, c_int32,
+                                      c_float, _P, _P]),
+    "lnrf_tex_resolve": (c_int32, [POINTER(TexAtlas), _P, c_int32, c_int32, c_int32, _P, _P, _P]),
+    "lnrf_tex_fill": (c_int32, [POINTER(TexAtlas), _P, _P, _P, _P, _P, _P]),
 }
 
 _lib = None
